@@ -322,6 +322,55 @@ def live_pmc(G, ticks=400, last=200, timeout_s=180, probe="probe_tick_min.py", e
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, sp, episodes, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files under `path`.
+      leaf_planes [G,3,S,S], policy [G,C], value [G]   the forward's input and outputs of the last tick (one row per game)
+      episode_header [E,4]                            game, seq, T, final value of every episode of the last hand-off, by (game, seq)
+      episode_policies, episode_visits [P,C]          per ply of those episodes: the root policy and visit counts
+      episode_moves [P,2]                             per ply: last cell (-1 at the root of a game), action cell
+      episode_keys [P,2K]                             per ply: the K-word position key (include/af_engine.h) as 32-bit halves
+    Integers are exact in the float type they are stored in.  Over DUMP_LIMIT_BYTES the games and the episodes are thinned to a
+    sample drawn with `seed` (sample_games / sample_episodes hold the indices kept).  -> summary for the JSON line."""
+    planes = sp.planes.cpu().numpy()
+    policy = sp.policy.cpu().numpy()
+    value = sp.value.cpu().numpy()
+    episodes = sorted(episodes, key=lambda e: (int(e["game"]), int(e["seq"])))
+    T = np.array([int(e["T"]) for e in episodes], np.int64)
+    per_game = planes.nbytes + policy.nbytes + value.nbytes
+    per_ply = 2 * 4 * sp.C + 2 * 8 + 2 * 8 * sp.engine.KW2       # policies, visits, moves, keys as float64 halves
+    total = per_game + int(T.sum()) * per_ply + 32 * len(episodes)
+    arrays = {}
+    keep_g, keep_e = np.arange(sp.G), np.arange(len(episodes))
+    if total > DUMP_LIMIT_BYTES:
+        frac = 0.95 * DUMP_LIMIT_BYTES / total
+        rng = np.random.RandomState(seed)
+        keep_g = np.sort(rng.choice(sp.G, max(1, int(sp.G * frac)), replace=False))
+        keep_e = np.sort(rng.choice(len(episodes), int(len(episodes) * frac), replace=False)) if len(episodes) else keep_e
+        arrays["sample_games"] = keep_g.astype(np.float64)
+        arrays["sample_episodes"] = keep_e.astype(np.float64)
+    arrays["leaf_planes"] = planes[keep_g]
+    arrays["policy"] = policy[keep_g]
+    arrays["value"] = value[keep_g]
+    kept = [episodes[i] for i in keep_e]
+    arrays["episode_header"] = np.array([[e["game"], e["seq"], e["T"], e["final_value"]] for e in kept], np.float64).reshape(-1, 4)
+    cat = lambda k, shape: np.concatenate([e[k] for e in kept]) if kept else np.zeros(shape)
+    arrays["episode_policies"] = cat("policies", (0, sp.C)).astype(np.float32)
+    arrays["episode_visits"] = cat("visits", (0, sp.C)).astype(np.float32)
+    arrays["episode_moves"] = np.stack([cat("lasts", (0,)), cat("actions", (0,))], axis=1).astype(np.float64)
+    keys = cat("keys", (0, sp.engine.KW2)).astype(np.uint64)
+    arrays["episode_keys"] = np.ascontiguousarray(keys).view(np.uint32).reshape(len(keys), 2 * sp.engine.KW2).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "bytes": int(sum(a.nbytes for a in arrays.values())), "sampled": "sample_games" in arrays,
+            "episodes": len(kept), "plies": int(len(arrays["episode_moves"])),
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 FP32_LEG_MODE = 1      # the fp32-MFMA path (Winograd register ring): 3.48 ms per 4096 positions vs 1.42 (tools/probe_arith_width.py, profiles/r6_02)
 
 EXTRA_LEGS = {
@@ -497,7 +546,13 @@ def main():
     ap.add_argument("--net", default="hip", choices=["hip", "torch", "deep-bf16", "deep-bf16-torch"],
                     help="hip (default): the hand-written kernels, fails without libaf_net.so; torch: PyTorch-ROCm ops "
                          "(reference only); deep-bf16 = BASELINE configs[4]: 8-block width-128 net in bf16 (use with --games 8192)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB): the forward's input and outputs of the last tick and the episodes of the last hand-off; "
+                         "the same arguments give the same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker > 0:
         return _cpu_worker(args)
 
@@ -591,6 +646,25 @@ def main():
     SAMPLE = 8                                        # eager, event-timed ticks per step in graph mode (~2 % of a step's ticks)
 
     stepno = {"n": 0}
+    # a step ends at the first poll that reads the target, and the poll reads the progress words as of the end of the PREVIOUS replay
+    # (the device stays busy with the newest one).  SelfPlayEngine.progress_lagged() reads the one pinned copy that every replay
+    # writes, which the newest replay may already have overwritten when the host comes late: the step boundaries, and with them
+    # everything the run computes, would depend on timing.  Here every replay's words go to a slot of their own.
+    lag = {"host": torch.zeros((2, 2), dtype=torch.int64, pin_memory=True), "events": [torch.cuda.Event(), torch.cuda.Event()],
+           "n": 0}
+
+    def post_progress():
+        i = lag["n"] % 2
+        sp.engine.progress_async(lag["host"][i].data_ptr(), stream)
+        lag["events"][i].record(torch.cuda.current_stream(dev))
+        lag["n"] += 1
+
+    def progress_lagged():
+        if lag["n"] < 2:
+            return 0
+        i = lag["n"] % 2                              # the previous replay's slot
+        lag["events"][i].synchronize()
+        return int(lag["host"][i, 0])
 
     def run_step(target):
         sample = use_graph and timing["on"]
@@ -606,6 +680,7 @@ def main():
                     sp.run_ticks_graph(args.poll, stamped=True)
                 else:
                     sp.run_ticks_graph(args.poll, timed=timing["on"])     # returns at once
+                post_progress()
                 if sample and k >= at:
                     # the sample that times the two kernels: eager launches bracketed by HIP events on the launch stream, inside
                     # the timed region, issued while the replay above keeps the device busy (no launch latency inside the
@@ -614,7 +689,7 @@ def main():
                         one_tick()
                     sample = False
                 k += 1
-                plies, _ = sp.progress_lagged()       # as of the previous replay: the device stays busy with the newest one
+                plies = progress_lagged()             # as of the previous replay: the device stays busy with the newest one
                 if plies >= target and sample:        # a short step: it still carries its sample
                     for _ in range(SAMPLE):
                         one_tick()
@@ -637,6 +712,7 @@ def main():
         gat = afdist.EpisodeGather(world, rank, comm_dev, EP_CAP, 2 * sp.engine.KW2 + 2 * C + 2, games_per_rank=G)
 
     handoff = {"s": 0.0, "n": 0}
+    handed = {"packs": []}                            # what the latest collect() received (views; read only by --dump-outputs)
 
     def collect(last=False):
         # header-only accounting: no per-episode host work on any rank between sp.check() and the next tick
@@ -647,9 +723,11 @@ def main():
             buf = sp.collect_episodes(EP_CAP, unpack=False)
             posted["buf"] = None
             n_eps, n_plies = (int(buf[0]), int(buf[1])) if buf is not None else (0, 0)
+            handed["packs"] = [buf] if buf is not None else []
         else:
             got = gat.flush(unpack=False) if last else gat.collect(unpack=False)
             n_eps, n_plies = sum(p.n for p in got), sum(p.plies for p in got)
+            handed["packs"] = got
             for p in got:                             # (rank 0 only; headers only: who sent what, and the largest global game id)
                 gathered["by_rank"][p.rank] += p.n
                 if p.n:
@@ -708,6 +786,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     power_report = power.stop() if power is not None else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            from alphafive_amd.engine import unpack_episodes
+            eps = [e for b in handed["packs"] for e in unpack_episodes(b, EP_CAP)]
+        else:
+            eps = [e for p in handed["packs"] for e in p.episodes()]
+        dumped = dump_outputs(args.dump_outputs, sp, eps, seed=args.seed)
     gathered_in_region = gathered["episodes"] - gathered_at_t0
     timing["on"] = False
     ticks_timed = sp.ticks - ticks0
@@ -970,6 +1056,8 @@ def main():
                 cb.update({"all_cores_value": ac["value"], "all_cores_cores": ac["cores"], "all_cores_host_cores": ac["host_cores"],
                            "all_cores_sample": ac["sample"]})
             out["cpu_baseline"] = cb
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.age_plies > 0:
             out["config"]["aged"] = ("games aged %d plies at %d sims/move before the %d full-budget warm-up steps (untimed)"
                                      % (args.age_plies, args.age_sims, args.warmup))

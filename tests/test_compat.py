@@ -1,15 +1,13 @@
 """alphafive_amd.compat.install(): the reference's scripts keep their import lines (main.py:2-15, self_play.py:2-8,
 choose_best_player.py:2-9) and get the engine's classes; the replay pickles stay interchangeable with the reference's
 own utils.RandomStack (utils.py:29-57)."""
-import importlib.util
 import os
+import pickle
 import random
 import sys
 
 import numpy as np
 import pytest
-
-REF = "/root/reference"
 
 
 @pytest.fixture
@@ -102,16 +100,9 @@ def _episode(S, T, rng):
     return rec
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "utils.py")), reason="build container only: needs /root/reference")
-def test_replay_pickles_load_in_the_reference_randomstack(tmp_path, monkeypatch):
-    """RandomStack.save here -> utils.RandomStack.load of the unmodified reference (and back): same records, same
-    bookkeeping, and the same augmented batch under the same seeds."""
+def build_stack():
+    """The stack both sides of the pickle exchange are checked on (tests/golden/make_compat_randomstack.py builds the same)."""
     from alphafive_amd import utils as mine
-    spec = importlib.util.spec_from_file_location("af_reference_utils", os.path.join(REF, "utils.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    monkeypatch.chdir(tmp_path)
-    os.mkdir("data_buffer")
     rng = np.random.RandomState(3)
     S = 11
     a = mine.RandomStack(S, length=300)
@@ -119,22 +110,51 @@ def test_replay_pickles_load_in_the_reference_randomstack(tmp_path, monkeypatch)
     for i in range(14):
         T = int(rng.randint(22, 40))
         a.push(_episode(S, T, rng), mine.BLACK_WIN if T % 2 else mine.WHITE_WIN)
+    return a
+
+
+class _PlainUnpickler(pickle.Unpickler):
+    """pickle.load as the reference's RandomStack.load runs it (utils.py:43-49), in a process that has no alphafive_amd: a pickle
+    that names any class outside numpy and the builtins would not load there."""
+
+    def find_class(self, module, name):
+        if module.split(".")[0] not in ("numpy", "builtins", "copyreg", "_codecs"):
+            raise pickle.UnpicklingError("%s.%s is not loadable without alphafive_amd" % (module, name))
+        return super().find_class(module, name)
+
+
+def test_replay_pickles_load_in_the_reference_randomstack(tmp_path, monkeypatch, golden_dir):
+    """RandomStack.save here -> utils.RandomStack.load of the unmodified reference (and back): same records, same
+    bookkeeping, and the same augmented batch under the same seeds.  The reference's side is recorded in
+    tests/golden/compat_randomstack.npz (tests/golden/make_compat_randomstack.py)."""
+    from alphafive_amd import utils as mine
+    z = np.load(os.path.join(golden_dir, "compat_randomstack.npz"))
+    monkeypatch.chdir(tmp_path)
+    os.mkdir("data_buffer")
+    a = build_stack()
     a.save(60)
-    b = ref.RandomStack(S, length=300)
-    b.load(60)
-    assert len(b.data) == len(a.data) and b.data_len == a.data_len and b.result == a.result
-    assert (b.black_win, b.white_win) == (a.black_win, a.white_win)
-    for x, y in zip(a.data, b.data):
-        assert x[0] == y[0] and (x[1] == y[1]).all() and x[2:] == y[2:]
-    for st in (a, b):
-        np.random.seed(5)
-        random.seed(5)
-        st.batch = st.get_data(batch_size=64)
-    for x, y in zip(a.batch, b.batch):
-        assert x.dtype == y.dtype and (x == y).all()
+    loaded = {}
+    for stem in ("data", "data_len", "result"):
+        with open(os.path.join("data_buffer", "%s60.pkl" % stem), "rb") as f:
+            loaded[stem] = _PlainUnpickler(f).load()
+    assert loaded["data_len"] == a.data_len and loaded["result"] == a.result and len(loaded["data"]) == len(a.data)
+    # what the reference's load(60) made of these files
+    assert int(z["ref_n_data"]) == len(a.data) and z["ref_data_len"].tolist() == a.data_len and z["ref_result"].tolist() == a.result
+    assert (int(z["ref_black_win"]), int(z["ref_white_win"])) == (a.black_win, a.white_win)
+    ref_data = pickle.loads(z["ref_pkl_data"].tobytes())           # the records as the reference holds (and re-saves) them
+    assert len(ref_data) == len(a.data)
+    for x, y, w in zip(a.data, ref_data, loaded["data"]):
+        assert x[0] == y[0] == w[0] and (x[1] == y[1]).all() and (x[1] == w[1]).all() and x[2:] == y[2:] == w[2:]
+    np.random.seed(5)
+    random.seed(5)
+    batch = a.get_data(batch_size=64)
+    for x, k in zip(batch, ("ref_boards", "ref_weights", "ref_values", "ref_policies")):
+        assert x.dtype == z[k].dtype and x.shape == z[k].shape and (x == z[k]).all(), k
     # and the other way round: what the reference writes, this class loads
-    b.save(120)
-    c = mine.RandomStack(S, length=300)
+    for stem in ("data", "data_len", "result"):
+        with open(os.path.join("data_buffer", "%s120.pkl" % stem), "wb") as f:
+            f.write(z["ref_pkl_" + stem].tobytes())
+    c = mine.RandomStack(11, length=300)
     c.load(120)
     assert c.data_len == a.data_len and c.result == a.result and len(c.data) == len(a.data)
 

@@ -21,7 +21,16 @@ def _episode(rank, i, T, C=36, kw2=4):
                 lasts=rng.randint(-1, C, size=T).astype(np.int32), actions=rng.randint(0, C, size=T).astype(np.int32))
 
 
+def _stay_off_the_gpu():
+    """The gloo ranks are CPU processes.  On a GPU box EpisodeGather's torch.cuda.is_available() would open the device in every
+    one of them (and pin its buffers there): eight ranks next to the test process would be nine processes holding one GPU.  The
+    ranks see no device, as on a CPU box, and end with gloo's own barrier: dist.barrier() asks for the device count
+    (torch._C._get_accelerator), which opens the device too."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, q):
+    _stay_off_the_gpu()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -47,7 +56,7 @@ def _worker(rank, world, port, q):
     q.put((rank, [(e["game"], e["seq"], e["T"], e["final_value"], float(e["policies"].sum()),
                    int(e["visits"].sum()), int(e["keys"].sum() % 1000003)) for e in got], total, digest,
            [(e["game"], e["T"], int(e["visits"].sum())) for e in piped], lag, g.bytes_received))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -89,6 +98,7 @@ def test_gather_broadcast_allreduce(world):
 
 def _steady_worker(rank, world, port, q):
     """The steady-state shape of BASELINE configs[2]: every rank hands over ~160 episodes of ~26 plies at 11x11 per step."""
+    _stay_off_the_gpu()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -125,7 +135,7 @@ def _steady_worker(rank, world, port, q):
     wall_ms, host_ms = g.handoff_ms_per_step()
     q.put((rank, n_eps, n_plies, sum(b[1] for b in bufs) * (steps // 3), wall_ms, host_ms, allocs,
            [(e["game"], e["T"], int(e["actions"][0])) for e in sample]))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

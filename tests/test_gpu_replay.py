@@ -125,7 +125,7 @@ def test_trainer_consumes_device_batches():
     st.close()
 
 
-def test_closed_loop_self_play_replay_train_on_device(capsys):
+def test_closed_loop_self_play_replay_train_on_device(capsys, tmp_path):
     """train.train_loop (main.py:57-76) with every stage on the GPU: SelfPlayEngine -> DeviceRandomStack -> Trainer, the
     engine's hand-written evaluator picking up each weight update."""
     import types
@@ -140,7 +140,7 @@ def test_closed_loop_self_play_replay_train_on_device(capsys):
     S = 6
     cfg = make_cfg(board_size=S, goal=4, simulation_per_step=16, upper_simulation_per_step=24, batch_size=64)
     cfg.get_lr = lambda step: 1e-3
-    cfg.ckpt_path = "/tmp/af_closed_loop_ckpt"
+    cfg.ckpt_path = str(tmp_path / "ckpt")
     net = ResNet(S, device="cuda", seed=0)
     before = {k: v.copy() for k, v in net.variables.items()}
     sp = SelfPlayEngine(cfg, 64, net.select_backend("hip"), device=0, seed=1)

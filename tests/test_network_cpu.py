@@ -1,4 +1,5 @@
 """Network rebuild (alphafive_amd.network) on torch-CPU vs the fp64 restatement; checkpoint reader."""
+import hashlib
 import os
 
 import numpy as np
@@ -49,9 +50,30 @@ def test_other_board_sizes_and_shape_checks():
         net.set_variables(bad)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/ckpt/checkpoint"), reason="reference checkpoint not present")
-def test_tensorbundle_reader_on_reference_checkpoint():
-    prefix = tensorbundle.resolve_checkpoint("/root/reference/ckpt")
+def _reference_checkpoint(directory):
+    """The checkpoint the reference ships (ckpt/: checkpoint, alphaFive-6960.index, alphaFive-6960.data-00000-of-00001), rebuilt
+    byte for byte in `directory` from tests/golden/ckpt_6960.npz (tests/golden/make_ckpt_6960.py) and the weights npz: the
+    .data file is the variables' float32 bytes at the recorded offsets, checked against the recorded SHA-256."""
+    directory = str(directory)
+    os.makedirs(directory, exist_ok=True)
+    g = np.load(os.path.join(GOLDEN, "ckpt_6960.npz"))
+    data = bytearray(int(g["data_size"]))
+    with np.load(W) as z:
+        for k, off in zip(g["data_names"].tolist(), g["data_offsets"].tolist()):
+            b = np.ascontiguousarray(z[k], np.float32).tobytes()
+            data[off:off + len(b)] = b
+    assert hashlib.sha256(bytes(data)).hexdigest() == str(g["data_sha256"])
+    prefix = os.path.join(directory, "alphaFive-6960")
+    for path, content in ((prefix + ".data-00000-of-00001", bytes(data)), (prefix + ".index", g["index"].tobytes()),
+                          (os.path.join(directory, "checkpoint"), g["checkpoint"].tobytes())):
+        with open(path, "wb") as f:
+            f.write(content)
+    return prefix
+
+
+def test_tensorbundle_reader_on_reference_checkpoint(tmp_path):
+    _reference_checkpoint(tmp_path / "ckpt")
+    prefix = tensorbundle.resolve_checkpoint(str(tmp_path / "ckpt"))
     assert prefix.endswith("alphaFive-6960")
     vs = tensorbundle.load_bundle(prefix)
     shapes = variable_shapes(11)
@@ -84,11 +106,10 @@ def test_tensorbundle_writer_roundtrip(tmp_path):
     assert (net2.eval(x)[0] == net.eval(x)[0]).all()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/ckpt/checkpoint"), reason="reference checkpoint not present")
 def test_tensorbundle_writer_reproduces_the_reference_checkpoint_bytes(tmp_path):
     """Re-writing the tensors of ckpt/alphaFive-6960 must give byte-identical .data and .index files
     (tensor order, offsets, masked crc32c per tensor, SSTable block/restart/footer layout)."""
-    src = "/root/reference/ckpt/alphaFive-6960"
+    src = _reference_checkpoint(tmp_path / "ref")
     prefix = str(tmp_path / "alphaFive-6960")
     tensorbundle.save_bundle(prefix, tensorbundle.load_bundle(src))
     for ext in (".data-00000-of-00001", ".index"):
