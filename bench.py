@@ -2,6 +2,7 @@
 """bench.py — self-play moves/sec (BASELINE.json metric) on N MI355X of one node.
 
     python bench.py                              # = --gpus 1 --steps 20 --warmup 8
+    python bench.py --full                       # ... and everything beyond the headline (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,6 +19,11 @@ max-over-ranks wall time.  The metric is a STEADY-STATE rate: the 
 8 plies per game and time 20 more, so finished episodes, store collection and game restarts are
 inside the timed region; a run in which no episode finished is reported with "value": null.  Inputs are synthetic (all games start from the empty board) and
 resident in HBM; nothing crosses PCIe on the tick path.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line (with the
+figures its timed steps measured on the way).  --full adds what takes work of its own after the timed steps: the CPU baselines, the
+other BASELINE configurations and the fp32-MFMA precision as legs in child processes, the live leaf batch through PyTorch's fp32
+ops, rocprofv3 counter passes, the measured copy bandwidth, and the untimed drain that checks rank 0 received every episode.
 """
 import argparse
 import json
@@ -391,17 +397,18 @@ PROCESS_T0 = time.time()
 
 def extra_config_legs(timeout_s=240, wall_budget_s=600.0):
     """Short steady-state legs of the two other single-GPU configurations BASELINE.json names, run as child processes of this
-    same file after the default workload (so the driver's one `python bench.py` sees them): flat keys configN_* on the JSON
-    line plus the children's own lines under "extra_configs".  A leg that fails or times out is reported as an error string."""
+    same file after the default workload of a --full run (so one `python bench.py --full` sees them): flat keys configN_* on the
+    JSON line plus the children's own lines under "extra_configs".  A leg that fails or times out is reported as an error string."""
     import subprocess
     flat, full = {}, {}
     for name, leg in EXTRA_LEGS.items():
-        # the whole default run is meant to finish within minutes also on a box that pages the image in for the first time (every
+        # the whole --full run is meant to finish within minutes also on a box that pages the image in for the first time (every
         # child start then costs tens of seconds): a leg that would start past the budget is skipped and says so
         if time.time() - PROCESS_T0 > wall_budget_s - 60.0:
             flat[name + "_error"] = "skipped: %.0f s of the run's %.0f-s wall budget were used before this leg" % (time.time() - PROCESS_T0, wall_budget_s)
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-pmc", "--no-extra-configs"] + leg
+        # --full: a leg's line carries the comparison with PyTorch's fp32 ops (config2_fp32mfma_dv_max_vs_torch_fp32, ...)
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-pmc", "--no-extra-configs"] + leg
         t0 = time.time()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s,
@@ -524,8 +531,13 @@ def main():
                     help="graph (default): the steady-state loop replays --poll x (tick + forward) as ONE HIP graph and reads the "
                          "progress words one replay late, so the host never drains the device; one eager chunk per step carries the "
                          "HIP events that time the tick kernel and the forward.  eager: every launch issued from Python (r3's loop; A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="take roofline.traffic from profiles/ instead of two rocprofv3 counter passes in this run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: CPU baselines, the legs of "
+                         "the other configurations and precisions, the live leaf batch against PyTorch's fp32 ops, rocprofv3 counter "
+                         "passes, the measured copy bandwidth and the drain that checks rank 0 received every episode (the --no-* "
+                         "options below leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the two rocprofv3 counter passes: roofline.traffic from profiles/")
     ap.add_argument("--age-plies", type=int, default=0,
                     help="before the warm-up steps, age the games this many plies at --age-sims simulations per move (untimed): the "
                          "games desynchronise and reach the mixed-phase population of the steady state ~40x faster than full-budget "
@@ -533,16 +545,16 @@ def main():
     ap.add_argument("--age-sims", type=int, default=16)
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the short steady-state legs of BASELINE configs[3] (15x15, 800 sims) and configs[4] (8-block bf16 net, "
-                         "8192 games) that the default N=1 run appends as flat keys config4_* / config5_*")
+                         "8192 games) that the default N=1 run with --full appends as flat keys config4_* / config5_*")
     ap.add_argument("--eval-memo", default="", metavar="LOG2_BUCKETS:MAX_STONES",
                     help="share evaluations between the games of a rank (include/af_engine.h ABI v5; e.g. 22:5).  Off for the headline: "
-                         "the default run measures it in a leg of its own (config2_memo_*)")
+                         "the default run with --full measures it in a leg of its own (config2_memo_*)")
     ap.add_argument("--pipe-values", action="store_true",
                     help="W / Q in fp64: the arithmetic of main.py's pipe-fed workers (networkAPI.py:72); default = the pv_fn path")
     ap.add_argument("--conv-mode", type=int, default=5, choices=[1, 5],
                     help="af_net_tune(0, .): 5 (default) = fp16 split-operand implicit GEMM (22 mantissa bits, 3 fp16 MFMA products per "
-                         "MAC); 1 = the fp32-MFMA Winograd path of af_net.hip (24 bits, the reference's width).  The default run measures "
-                         "mode 1 in a leg of its own (config2_fp32mfma_*)")
+                         "MAC); 1 = the fp32-MFMA Winograd path of af_net.hip (24 bits, the reference's width).  The default run with "
+                         "--full measures mode 1 in a leg of its own (config2_fp32mfma_*)")
     ap.add_argument("--net", default="hip", choices=["hip", "torch", "deep-bf16", "deep-bf16-torch"],
                     help="hip (default): the hand-written kernels, fails without libaf_net.so; torch: PyTorch-ROCm ops "
                          "(reference only); deep-bf16 = BASELINE configs[4]: 8-block width-128 net in bf16 (use with --games 8192)")
@@ -835,26 +847,28 @@ def main():
         dist.all_gather_object(ranks_info, me)
     ranks_seen = int(ones.item())
     backend = dist.get_backend() if world > 1 else None
-    # untimed: drain the episodes still waiting on the devices (more than EP_CAP may finish in a step, and the gather runs one
-    # step behind), so that the line can state "rank 0 holds every episode the ranks finished": cumulative counts since engine
-    # creation on both sides (the engines' device counters vs the headers rank 0 received)
-    fin_total = torch.tensor([float(ct1["episodes"])], device=comm_dev, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(fin_total, op=dist.ReduceOp.SUM)
-    got_total = torch.zeros(1, device=comm_dev, dtype=torch.float64)
-    for _ in range(16):
-        got_total[0] = float(gathered["episodes"])
+    gathered_total = finished_total = None
+    if args.full:
+        # untimed: drain the episodes still waiting on the devices (more than EP_CAP may finish in a step, and the gather runs one
+        # step behind), so that the line can state "rank 0 holds every episode the ranks finished": cumulative counts since engine
+        # creation on both sides (the engines' device counters vs the headers rank 0 received)
+        fin_total = torch.tensor([float(ct1["episodes"])], device=comm_dev, dtype=torch.float64)
         if world > 1:
-            dist.broadcast(got_total, src=0)
-        if got_total.item() >= fin_total.item():
-            break
-        hand_off()
-        collect(last=True)
-    gathered_total, finished_total = int(got_total.item()), int(fin_total.item())
+            dist.all_reduce(fin_total, op=dist.ReduceOp.SUM)
+        got_total = torch.zeros(1, device=comm_dev, dtype=torch.float64)
+        for _ in range(16):
+            got_total[0] = float(gathered["episodes"])
+            if world > 1:
+                dist.broadcast(got_total, src=0)
+            if got_total.item() >= fin_total.item():
+                break
+            hand_off()
+            collect(last=True)
+        gathered_total, finished_total = int(got_total.item()), int(fin_total.item())
 
     if rank == 0:
         arith = None
-        if deep is None and args.net == "hip":
+        if args.full and deep is None and args.net == "hip":
             # arithmetic width on the line: the live leaf batch of the last tick through the kernels once more
             # (same bits: the forward is deterministic) and through ResNet.eval_torch = PyTorch-ROCm fp32 ops, product side, no oracle
             pl, vl = (x_.clone() for x_ in pv(sp.planes))
@@ -911,10 +925,10 @@ def main():
                 traffic_net = prof["net_forward_bytes_per_launch"]["corrected"]
                 traffic_tick = prof["tick_kernel_bytes_per_launch"]["corrected"]
                 traffic_src = tp_name + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)"
-                # ... and, unless --no-pmc, collected again in THIS run: two short rocprofv3 counter passes over the same kernels
-                # (child processes, after the timed region; the net's traffic does not depend on the game phase, the tick
+                # ... and, with --full unless --no-pmc, collected again in THIS run: two short rocprofv3 counter passes over the same
+                # kernels (child processes, after the timed region; the net's traffic does not depend on the game phase, the tick
                 # kernel's does, so tree_roofline keeps the steady-state figure of the file)
-                live = None if (args.no_pmc or world > 1) else live_pmc(G)
+                live = None if (not args.full or args.no_pmc or world > 1) else live_pmc(G)
                 if live is not None and live.get("traffic"):
                     pmc = live
                     traffic_net = live["traffic"]
@@ -927,7 +941,7 @@ def main():
                      "kernel": "deep net forward (PyTorch-ROCm ops, whole forward timed)"} if args.net.endswith("torch") else
                     {"backend": "hip (af_tower_bf16.hip: bf16 MFMA stem + implicit-GEMM tower, weight-stationary, LDS-DMA staging + heads 1x1 convs + MFMA dense layers / softmax)",
                      "kernel": "deep net forward = af_tower_stem + 16x af_tower_conv + af_tower_heads + af_tower_dense (whole forward timed; af_tower_conv carries 99 % of the FLOPs)"})
-        copy_gbs = copy_bandwidth_gbs(dev)
+        copy_gbs = copy_bandwidth_gbs(dev) if args.full else None
         out = {
             "metric": "self-play moves/sec (%dx%d, %d sims/move)" % (cfg.board_size, cfg.board_size, args.sims),
             "value": (total_plies / t) if steady else None, "unit": "moves/s",
@@ -955,8 +969,8 @@ def main():
                        "terminal_frac": d["terminals"] / max(1, d["sims"]),
                        "episodes_gathered": gathered_in_region, "episodes_finished_in_timed_region": int(eps_all.item()),
                        "eval_memo": memo_report,
-                       # self-verification of the N>1 line: the process group as it really was, and rank 0's receipt of every
-                       # episode any rank finished since its engine was created (after an untimed drain of what was still queued)
+                       # self-verification of the N>1 line: the process group as it really was, and (--full) rank 0's receipt of
+                       # every episode any rank finished since its engine was created (after an untimed drain of what was still queued)
                        "ranks_seen": ranks_seen, "backend": backend if world > 1 else "none (single process)",
                        "launcher": "bench.py spawn_ranks" if os.environ.get("AF_BENCH_SPAWNED") == "1" else
                                    ("torch.distributed.run / external" if world > 1 else "single process"),
@@ -965,7 +979,7 @@ def main():
                        "per_rank": [{"rank": r["rank"], "episodes_finished": r["episodes_finished"], "plies": r["plies"],
                                      "elapsed_s": r["elapsed_s"]} for r in ranks_info],
                        "episodes_gathered_total": gathered_total, "episodes_finished_total_all_ranks": finished_total,
-                       "gathered_equals_finished": gathered_total == finished_total,
+                       "gathered_equals_finished": gathered_total == finished_total if args.full else None,
                        # N > 1: whose episodes rank 0 holds, read off the packed headers it received (source rank r's games are
                        # the global ids r*G .. r*G + G-1), against every rank's own device counter
                        "episodes_gathered_by_source_rank": gathered["by_rank"] if world > 1 else None,
@@ -994,7 +1008,7 @@ def main():
             "tree_roofline": {"kernel": "af_tick_kernel<%d>" % (2 if C <= 128 else 4), "bound": "hbm", "achieved": tree_gbs,
                               "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": tree_gbs / PEAK_HBM_GBS, "traffic": traffic_tick,
                               "ms_per_launch": tick_ms, "bytes_per_launch": tree_bytes(d, C) / n_ticks,
-                              "peak_measured_copy": copy_gbs, "frac_of_measured_copy": tree_gbs / copy_gbs,
+                              "peak_measured_copy": copy_gbs, "frac_of_measured_copy": tree_gbs / copy_gbs if copy_gbs else None,
                               "note": "SURVEY 8d bound (HBM); PMC (profiles/r1_16) shows the kernel limited by per-game serial latency and fp64 VALU work of the noise generator"},
             "time_split": {"tree_ms_per_tick": tick_ms, "net_ms_per_tick": net_ms,
                            # what a tick costs beyond its two kernels: launch gaps, host polls, the hand-off (<= 5 us)
@@ -1043,7 +1057,7 @@ def main():
             out["invalid"] = ("no episode finished inside the run: this is an opening-phase rate, not the steady-state metric "
                               "(SURVEY 8d); use the defaults (--warmup 8 --steps 20)")
             out["opening_phase_moves_per_s"] = total_plies / t
-        if not args.no_cpu_baseline and world == 1:            # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:            # reported baseline: rank 0 at N=1 only
             w11 = weights if cfg.board_size == 11 else None
             cb = cpu_baseline(cfg, w11)                                            # the bench's own workload, 1 core
             # (1) config 1 (eval mode, whole game), (2) every usable core on complete episodes, (3) tree only.
@@ -1063,7 +1077,7 @@ def main():
                                      % (args.age_plies, args.age_sims, args.warmup))
         default_workload = (world == 1 and deep is None and cfg.board_size == 11 and G == 4096 and args.sims == 500
                             and not args.pipe_values and args.net == "hip")
-        if default_workload and not args.no_extra_configs:
+        if args.full and default_workload and not args.no_extra_configs:
             sp.close()
             sp = None
             torch.cuda.empty_cache()

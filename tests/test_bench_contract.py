@@ -1,4 +1,4 @@
-"""The one JSON line `python bench.py` prints, checked on the line the GPU box produced last (committed under profiles/): the
+"""The one JSON line `python bench.py --full` prints, checked on the line the GPU box produced last (committed under profiles/): the
 keys the driver's contract names, the roofline / cpu_baseline objects, and the arithmetic that ties them together."""
 import glob
 import json
@@ -79,18 +79,23 @@ def test_extra_config_legs_are_flat_scalars():
     assert d["config1_player_moves_per_s"] > 50                              # the single-launch small-batch forward (r5: 42)
 
 
-@pytest.mark.gpu
-def test_a_fresh_bench_run_prints_the_contract_line():
-    """the checks above read a committed artefact, so they pass whatever bench.py prints today.  This one runs
-    bench.py now (short: 2 timed steps on 512 games, no CPU baseline / counter passes / extra legs) and checks the line it prints."""
+def _fresh_line(*extra):
+    """Run bench.py now, short (2 timed steps on 512 games), and return the one line it prints."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--games", "512", "--steps", "2", "--warmup", "1", "--age-plies", "30",
-                        "--no-cpu-baseline", "--no-pmc", "--no-extra-configs"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--games", "512", "--steps", "2", "--warmup", "1", "--age-plies", "30"]
+                       + list(extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-800:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_a_fresh_bench_run_prints_the_contract_line():
+    """the checks above read a committed artefact, so they pass whatever bench.py prints today.  This one runs a plain
+    bench.py now and checks the line it prints: the headline and what the timed steps measured, none of what --full adds."""
+    d = _fresh_line()
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "tree_roofline", "time_split"):
         assert k in d, k
@@ -104,6 +109,22 @@ def test_a_fresh_bench_run_prints_the_contract_line():
     assert abs(plies - 2 * 512) < 0.25 * 2 * 512                 # a step commits about one ply per game
     assert "rank0_handoff_ms_per_step" in d["config"] and d["config"]["rank0_handoff_ms_per_step"] < 5.0
     assert abs(d["time_split"]["outside_kernels_us_per_tick"]) < 100
+    assert "cpu_baseline" not in d and "dv_max_vs_torch_fp32" not in r_ and d["tree_roofline"]["peak_measured_copy"] is None
+    assert d["config"]["gathered_equals_finished"] is None
+
+
+@pytest.mark.gpu
+def test_a_full_bench_run_adds_its_checks():
+    """--full, after the same timed steps: the live leaf batch through PyTorch's fp32 ops, the measured copy bandwidth and the
+    untimed drain after which rank 0 holds every finished episode (CPU baselines left out: a minute of host time)."""
+    d = _fresh_line("--full", "--no-cpu-baseline")
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "moves/s" and "cpu_baseline" not in d
+    r_ = d["roofline"]
+    assert r_["operand_mantissa_bits"] == 22 and 0 < r_["dv_max_vs_torch_fp32"] < 5e-5 and 0 < r_["dp_max_vs_torch_fp32"] < 5e-5
+    t = d["tree_roofline"]
+    assert t["peak_measured_copy"] > 0 and abs(t["frac_of_measured_copy"] - t["achieved"] / t["peak_measured_copy"]) < 1e-9
+    c = d["config"]
+    assert c["gathered_equals_finished"] and c["episodes_gathered_total"] == c["episodes_finished_total_all_ranks"] > 0
 
 
 def test_plain_python_gpus_n_spawns_ranks_and_a_failing_rank_ends_the_job():

@@ -158,8 +158,8 @@ def test_memo_at_the_metric_settings_complete_episodes_equal_the_oracle():
 
 
 def test_bench_reports_the_memo_leg_keys():
-    """`bench.py --eval-memo L:K` (what the default run starts as its config2_memo leg): the line says what the memo did in the timed
-    region of rank 0's engine, and the headline keys keep their meaning."""
+    """`bench.py --eval-memo L:K` (what the default run with --full starts as its config2_memo leg): the line says what the memo did
+    in the timed region of rank 0's engine, and the headline keys keep their meaning."""
     import json
     import subprocess
     import sys

@@ -70,7 +70,7 @@ def test_two_ranks_produce_the_episodes_of_one_big_engine(tmp_path):
 
 def test_bench_two_ranks_prints_one_consistent_line():
     r = _launch([os.path.join(REPO, "bench.py"), "--gpus", "2", "--games", "96", "--board", "6", "--sims", "30", "--upper", "40",
-                 "--steps", "36", "--warmup", "4", "--no-cpu-baseline"], extra_env={"AF_BENCH_SHARE_GPU": "1"})
+                 "--steps", "36", "--warmup", "4", "--full", "--no-cpu-baseline"], extra_env={"AF_BENCH_SHARE_GPU": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                 # rank 0 only
@@ -100,7 +100,7 @@ def test_plain_python_bench_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", AF_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--games", "96", "--board", "6", "--sims", "30",
-                        "--upper", "40", "--steps", "36", "--warmup", "4", "--no-cpu-baseline"], cwd=REPO, env=env,
+                        "--upper", "40", "--steps", "36", "--warmup", "4", "--full", "--no-cpu-baseline"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -137,7 +137,7 @@ def test_bench_four_ranks_dry_run_on_one_gpu():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", AF_BENCH_SHARE_GPU="1")
     G, N = 256, 4
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(N), "--games", str(G), "--board", "7", "--sims", "40",
-                        "--upper", "60", "--steps", "44", "--warmup", "4", "--no-cpu-baseline"], cwd=REPO, env=env,
+                        "--upper", "60", "--steps", "44", "--warmup", "4", "--full", "--no-cpu-baseline"], cwd=REPO, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
