@@ -29,7 +29,9 @@ struct af_replay {
     size_t pinned_bytes = 0;
     float* wtab = nullptr;       // [max_T + 1][max_T] construct_weights rows (af_replay_set_weights)
     int max_T = 0;
-    int32_t* err = nullptr;      // device flag: a packed append whose T did not match the buffer
+    int32_t* err = nullptr;      // device flags: [0] a packed append whose T did not match the buffer, [1] a malformed state string
+    char* stage = nullptr;       // contiguous device block an export gathers into / a state-string append uploads its text to
+    size_t stage_bytes = 0;
 };
 
 struct SampleArgs {
@@ -132,12 +134,156 @@ __global__ __launch_bounds__(256) void af_replay_append_packed_kernel(PackedArgs
     }
 }
 
+// One workgroup per exported position: gathers logical position `first + b` out of the five ring arrays into the contiguous
+// staging block (the ring's wrap ends here) and writes its state string (utils.py:156-175: per row a run of c empties is
+// 'a' + c, '3' mine, '1' theirs, '/' ends the row), NUL-terminated and NUL-padded to `stride` = S*(S+1) + 1 bytes.
+struct ExportArgs {
+    const int8_t* boards;
+    const float* policies;
+    const int32_t* last;
+    const float* values;
+    const float* weights;
+    int8_t* out_boards;          // [n][C]
+    float* out_policies;         // [n][C]
+    int32_t* out_last;           // [n]
+    float* out_values;           // [n]
+    float* out_weights;          // [n]
+    char* out_states;            // [n][stride]
+    int64_t slot0;               // ring slot of the first exported position
+    int cap, S, C, stride;
+};
+
+__global__ __launch_bounds__(256) void af_replay_export_kernel(ExportArgs A) {
+    __shared__ int8_t cell[256];
+    __shared__ char rowtxt[16][17];                   // a row of S cells is at most S characters + its '/'
+    __shared__ int rowlen[16];
+    const int b = blockIdx.x, S = A.S, C = A.C, tid = threadIdx.x;
+    const int64_t slot = (A.slot0 + b) % A.cap;
+    for (int c = tid; c < C; c += blockDim.x) {
+        const int8_t v = A.boards[slot * C + c];
+        cell[c] = v;
+        A.out_boards[(size_t)b * C + c] = v;
+        A.out_policies[(size_t)b * C + c] = A.policies[slot * C + c];
+    }
+    if (tid == 0) {
+        A.out_last[b] = A.last[slot];
+        A.out_values[b] = A.values[slot];
+        A.out_weights[b] = A.weights[slot];
+    }
+    __syncthreads();
+    if (tid < S) {                                    // one thread per row
+        char* txt = rowtxt[tid];
+        int len = 0, run = 0;
+        for (int j = 0; j < S; ++j) {
+            const int v = cell[tid * S + j];
+            if (v == 0) { ++run; continue; }
+            if (run) { txt[len++] = (char)('a' + run); run = 0; }
+            txt[len++] = v > 0 ? '3' : '1';
+        }
+        if (run) txt[len++] = (char)('a' + run);
+        txt[len++] = '/';
+        rowlen[tid] = len;
+    }
+    __syncthreads();
+    char* out = A.out_states + (size_t)b * A.stride;
+    int total = 0, off = 0;
+    for (int r = 0; r < S; ++r) {
+        if (r == tid) off = total;
+        total += rowlen[r];
+    }
+    if (tid < S)
+        for (int i = 0; i < rowlen[tid]; ++i) out[off + i] = rowtxt[tid][i];
+    for (int i = total + tid; i < A.stride; i += blockDim.x) out[i] = 0;      // total <= S*(S+1) < stride
+}
+
+// One workgroup per appended position: decodes its state string (utils.py:178-196 state_to_board) into the ring's int8 board.
+// Everything derived from the text is checked before it indexes anything: a string that is not exactly S rows of exactly S
+// cells in the alphabet above, NUL-terminated inside `stride`, raises err[1] and writes nothing.
+struct StatesArgs {
+    const char* states;          // [n][stride] (device staging)
+    int8_t* boards;
+    int32_t* err;
+    int64_t slot0;               // ring slot of the first appended position
+    int cap, S, C, stride;
+};
+
+__global__ __launch_bounds__(256) void af_replay_append_states_kernel(StatesArgs A) {
+    __shared__ int8_t cell[256];
+    __shared__ int good;
+    const int b = blockIdx.x, S = A.S, C = A.C, tid = threadIdx.x;
+    for (int c = tid; c < C; c += blockDim.x) cell[c] = 0;
+    __syncthreads();
+    if (tid == 0) {
+        const char* s = A.states + (size_t)b * A.stride;
+        int i = 0, j = 0, ok = 1, ended = 0;
+        for (int p = 0; p < A.stride && ok; ++p) {
+            const int ch = (unsigned char)s[p];
+            if (ch == 0) { ended = 1; break; }
+            if (i >= S) { ok = 0; break; }                        // text after the S-th row
+            if (ch == '/') {
+                if (j != S) ok = 0;                               // the row stops short of S cells
+                ++i; j = 0;
+            } else if (ch == '1' || ch == '3') {
+                if (j >= S) { ok = 0; break; }
+                cell[i * S + j] = (int8_t)(ch == '3' ? 1 : -1);
+                ++j;
+            } else if (ch > 'a' && ch <= 'a' + S) {
+                if (j + (ch - 'a') > S) { ok = 0; break; }        // the run passes the end of the row
+                j += ch - 'a';
+            } else {
+                ok = 0;
+            }
+        }
+        good = ok && ended && i == S && j == 0;
+        if (!good) atomicExch(A.err + 1, 1);
+    }
+    __syncthreads();
+    if (!good) return;
+    const int64_t slot = (A.slot0 + b) % A.cap;
+    for (int c = tid; c < C; c += blockDim.x) A.boards[slot * C + c] = cell[c];
+}
+
+static int ensure_err(af_replay* r) {
+    if (r->err) return AF_REPLAY_OK;
+    RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->err), 8));
+    RP_HIP_OK(hipMemset(r->err, 0, 8));
+    return AF_REPLAY_OK;
+}
+
+static int ensure_stage(af_replay* r, size_t bytes) {
+    if (bytes <= r->stage_bytes) return AF_REPLAY_OK;
+    if (r->stage) (void)hipFree(r->stage);
+    r->stage = nullptr; r->stage_bytes = 0;
+    RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->stage), bytes));
+    r->stage_bytes = bytes;
+    return AF_REPLAY_OK;
+}
+
 static int ensure_pinned(af_replay* r, size_t bytes) {
     if (bytes <= r->pinned_bytes) return AF_REPLAY_OK;
     if (r->pinned) (void)hipHostFree(r->pinned);
     r->pinned = nullptr; r->pinned_bytes = 0;
     RP_HIP_OK(hipHostMalloc(&r->pinned, bytes, hipHostMallocDefault));
     r->pinned_bytes = bytes;
+    return AF_REPLAY_OK;
+}
+
+// n positions into the slots behind the tail (host pointers; `boards` may be null: af_replay_append_states decodes them on the
+// device).  The ring wraps: copy in up to two runs.  `count` is the caller's to move.
+static int copy_in(af_replay* r, hipStream_t st, int n, const int8_t* boards, const float* policies, const int32_t* last_cell,
+                   const float* values, const float* weights) {
+    const size_t C = r->C;
+    int done = 0;
+    while (done < n) {
+        const int64_t slot = (r->head + r->count + done) % r->cap;
+        const int run = (int)((int64_t)(n - done) < r->cap - slot ? (n - done) : r->cap - slot);
+        if (boards) RP_HIP_OK(hipMemcpyAsync(r->boards + slot * C, boards + (size_t)done * C, (size_t)run * C, hipMemcpyHostToDevice, st));
+        RP_HIP_OK(hipMemcpyAsync(r->policies + slot * C, policies + (size_t)done * C, (size_t)run * C * 4, hipMemcpyHostToDevice, st));
+        RP_HIP_OK(hipMemcpyAsync(r->last + slot, last_cell + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
+        RP_HIP_OK(hipMemcpyAsync(r->values + slot, values + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
+        RP_HIP_OK(hipMemcpyAsync(r->weights + slot, weights + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
+        done += run;
+    }
     return AF_REPLAY_OK;
 }
 
@@ -150,6 +296,7 @@ const char* af_replay_strerror(int code) {
         case AF_REPLAY_ERR_HIP: return "HIP runtime error";
         case AF_REPLAY_ERR_FULL: return "replay ring full";
         case AF_REPLAY_ERR_RANGE: return "index outside the stored positions";
+        case AF_REPLAY_ERR_FORMAT: return "malformed state string";
         default: return "unknown error";
     }
 }
@@ -181,6 +328,7 @@ void af_replay_destroy(af_replay* r) {
     if (r->sel) (void)hipFree(r->sel);
     if (r->wtab) (void)hipFree(r->wtab);
     if (r->err) (void)hipFree(r->err);
+    if (r->stage) (void)hipFree(r->stage);
     if (r->pinned) (void)hipHostFree(r->pinned);
     delete r;
 }
@@ -202,21 +350,74 @@ int af_replay_append(af_replay* r, void* stream, int32_t n, const int8_t* boards
     if (r->count + n > r->cap) return AF_REPLAY_ERR_FULL;
     RP_HIP_OK(hipSetDevice(r->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t C = r->C;
-    // the ring wraps: copy in up to two runs
-    int done = 0;
-    while (done < n) {
-        const int64_t slot = (r->head + r->count + done) % r->cap;
-        const int run = (int)((int64_t)(n - done) < r->cap - slot ? (n - done) : r->cap - slot);
-        RP_HIP_OK(hipMemcpyAsync(r->boards + slot * C, boards + (size_t)done * C, (size_t)run * C, hipMemcpyHostToDevice, st));
-        RP_HIP_OK(hipMemcpyAsync(r->policies + slot * C, policies + (size_t)done * C, (size_t)run * C * 4, hipMemcpyHostToDevice, st));
-        RP_HIP_OK(hipMemcpyAsync(r->last + slot, last_cell + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
-        RP_HIP_OK(hipMemcpyAsync(r->values + slot, values + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
-        RP_HIP_OK(hipMemcpyAsync(r->weights + slot, weights + done, (size_t)run * 4, hipMemcpyHostToDevice, st));
-        done += run;
-    }
+    const int rc = copy_in(r, st, n, boards, policies, last_cell, values, weights);
+    if (rc) return rc;
     RP_HIP_OK(hipStreamSynchronize(st));               // pageable host memory: the caller may reuse its arrays on return
     r->count += n;
+    return AF_REPLAY_OK;
+}
+
+int32_t af_replay_state_stride(const af_replay* r) { return r ? r->S * (r->S + 1) + 1 : 0; }
+
+int af_replay_append_states(af_replay* r, void* stream, int32_t n, const char* states, int32_t state_stride, const float* policies,
+                            const int32_t* last_cell, const float* values, const float* weights) {
+    if (!r || n < 0 || (n > 0 && (!states || state_stride < 1 || !policies || !last_cell || !values || !weights))) return AF_REPLAY_ERR_ARG;
+    if (n == 0) return AF_REPLAY_OK;
+    if (r->count + n > r->cap) return AF_REPLAY_ERR_FULL;
+    RP_HIP_OK(hipSetDevice(r->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = ensure_err(r);
+    if (!rc) rc = ensure_stage(r, (size_t)n * state_stride);
+    if (rc) return rc;
+    // everything lands in slots behind the tail, which hold nothing until `count` moves: a rejected call leaves the ring as it was
+    RP_HIP_OK(hipMemcpyAsync(r->stage, states, (size_t)n * state_stride, hipMemcpyHostToDevice, st));
+    rc = copy_in(r, st, n, nullptr, policies, last_cell, values, weights);
+    if (rc) return rc;
+    StatesArgs a;
+    a.states = r->stage; a.boards = r->boards; a.err = r->err; a.slot0 = (r->head + r->count) % r->cap;
+    a.cap = r->cap; a.S = r->S; a.C = r->C; a.stride = state_stride;
+    hipLaunchKernelGGL(af_replay_append_states_kernel, dim3(n), dim3(256), 0, st, a);
+    RP_HIP_OK(hipGetLastError());
+    int32_t bad = 0;
+    RP_HIP_OK(hipMemcpyAsync(&bad, r->err + 1, 4, hipMemcpyDeviceToHost, st));
+    RP_HIP_OK(hipStreamSynchronize(st));               // pageable host memory: the caller may reuse its arrays on return
+    if (bad) {
+        RP_HIP_OK(hipMemset(r->err + 1, 0, 4));
+        return AF_REPLAY_ERR_FORMAT;
+    }
+    r->count += n;
+    return AF_REPLAY_OK;
+}
+
+int af_replay_export(af_replay* r, void* stream, int32_t first, int32_t n, char* states, int8_t* boards, float* policies,
+                     int32_t* last_cell, float* values, float* weights) {
+    if (!r || first < 0 || n < 0 || (n > 0 && (!policies || !last_cell || !values || !weights))) return AF_REPLAY_ERR_ARG;
+    if ((int64_t)first + n > r->count) return AF_REPLAY_ERR_RANGE;
+    if (n == 0) return AF_REPLAY_OK;
+    RP_HIP_OK(hipSetDevice(r->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t C = r->C, N = n, stride = (size_t)af_replay_state_stride(r);
+    // staging layout: policies | last | values | weights | boards | states (the 4-byte arrays first, so all stay aligned)
+    const int rc = ensure_stage(r, N * (C * 4 + 12 + C + stride));
+    if (rc) return rc;
+    ExportArgs a;
+    a.boards = r->boards; a.policies = r->policies; a.last = r->last; a.values = r->values; a.weights = r->weights;
+    a.out_policies = reinterpret_cast<float*>(r->stage);
+    a.out_last = reinterpret_cast<int32_t*>(a.out_policies + N * C);
+    a.out_values = reinterpret_cast<float*>(a.out_last + N);
+    a.out_weights = a.out_values + N;
+    a.out_boards = reinterpret_cast<int8_t*>(a.out_weights + N);
+    a.out_states = reinterpret_cast<char*>(a.out_boards + N * C);
+    a.slot0 = (r->head + first) % r->cap; a.cap = r->cap; a.S = r->S; a.C = r->C; a.stride = (int)stride;
+    hipLaunchKernelGGL(af_replay_export_kernel, dim3(n), dim3(256), 0, st, a);
+    RP_HIP_OK(hipGetLastError());
+    RP_HIP_OK(hipMemcpyAsync(policies, a.out_policies, N * C * 4, hipMemcpyDeviceToHost, st));
+    RP_HIP_OK(hipMemcpyAsync(last_cell, a.out_last, N * 4, hipMemcpyDeviceToHost, st));
+    RP_HIP_OK(hipMemcpyAsync(values, a.out_values, N * 4, hipMemcpyDeviceToHost, st));
+    RP_HIP_OK(hipMemcpyAsync(weights, a.out_weights, N * 4, hipMemcpyDeviceToHost, st));
+    if (boards) RP_HIP_OK(hipMemcpyAsync(boards, a.out_boards, N * C, hipMemcpyDeviceToHost, st));
+    if (states) RP_HIP_OK(hipMemcpyAsync(states, a.out_states, N * stride, hipMemcpyDeviceToHost, st));
+    RP_HIP_OK(hipStreamSynchronize(st));
     return AF_REPLAY_OK;
 }
 
@@ -229,10 +430,8 @@ int af_replay_set_weights(af_replay* r, const float* table_host, int32_t max_T) 
     const size_t bytes = (size_t)(max_T + 1) * max_T * 4;
     RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->wtab), bytes));
     RP_HIP_OK(hipMemcpy(r->wtab, table_host, bytes, hipMemcpyHostToDevice));
-    if (!r->err) {
-        RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->err), 4));
-        RP_HIP_OK(hipMemset(r->err, 0, 4));
-    }
+    const int rc = ensure_err(r);
+    if (rc) return rc;
     r->max_T = max_T;
     return AF_REPLAY_OK;
 }

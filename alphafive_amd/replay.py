@@ -8,6 +8,10 @@ and uploads the accepted episode once; push_packed() / iter_push_packed() take t
 instead: the host reads its header only and the plies are decoded on the device (no 5-tuples, no per-ply Python, no
 upload); get_data() draws (which positions, quarter turns, flip) on the host and runs the gather + 8-fold symmetry +
 board_to_inputs encoding as one kernel launch.
+
+Persistence: to_host() reads the ring out as a utils.RandomStack (one af_replay_export: the device writes the records' state
+strings), from_host() / load_records() put records back (af_replay_append_states: the device decodes them), and
+save_pickles() / load_pickles() exchange the reference's three data_buffer/*.pkl files (utils.py:29-57) on top of those.
 """
 import ctypes as C
 import os
@@ -46,6 +50,9 @@ def lib():
         L.af_replay_append_packed.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32]
         L.af_replay_set_weights.argtypes = [vp, fp, C.c_int32]
         L.af_replay_check.argtypes = [vp, vp]
+        L.af_replay_state_stride.argtypes = [vp]
+        L.af_replay_export.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.af_replay_append_states.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
         L.af_replay_strerror.argtypes = [C.c_int]
         L.af_replay_strerror.restype = C.c_char_p
         _lib = L
@@ -71,6 +78,10 @@ class _PackedEpisode(object):
 
 
 class DeviceRandomStack(utils.RandomStack):
+    """utils.RandomStack with the positions in HBM (module docstring).  `data` is None; what the host class keeps there is read
+    with to_host() and written with load_records() / from_host().  save() / load() are not the way to the reference's pickles
+    here: save_pickles() / load_pickles() are."""
+
     def __init__(self, board_size, length=2000, device=0, max_episode=None):
         super().__init__(board_size, length)
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -150,11 +161,88 @@ class DeviceRandomStack(utils.RandomStack):
         """Raises if a packed append found its buffer not to hold what the header said (synchronises the stream)."""
         _check(lib().af_replay_check(self._h, torch.cuda.current_stream(self.device).cuda_stream), "af_replay_check")
 
-    # ---- persistence is a host concern: use utils.RandomStack for the reference's pickles ----
+    # ---- persistence: the ring read out as / filled from the host class's records ----
     def save(self, s=""):
-        raise NotImplementedError("DeviceRandomStack keeps positions in HBM; use utils.RandomStack for data_buffer/*.pkl")
+        raise NotImplementedError("DeviceRandomStack keeps positions in HBM; use save_pickles() / load_pickles() for "
+                                  "data_buffer/*.pkl, to_host() / from_host() for a utils.RandomStack")
 
     load = save
+
+    def to_host(self):
+        """-> utils.RandomStack holding what this stack holds: `data` as the 5-tuples engine.assemble_episode produces and the
+        reference pickles (str, float32[S,S], (i, j) or None, float, np.float32) and the same length / data_len / result /
+        black_win / white_win.  One af_replay_export: the ring is gathered and the state strings are written on the device."""
+        S, n = self.board_size, self._size()
+        host = utils.RandomStack(S, self.length)
+        host.data_len, host.result = list(self.data_len), list(self.result)
+        host.black_win, host.white_win = self.black_win, self.white_win
+        if n == 0:
+            return host
+        stride = int(lib().af_replay_state_stride(self._h))
+        states = np.zeros(n, "S%d" % stride)
+        pol = np.empty((n, S, S), np.float32)
+        last = np.empty(n, np.int32)
+        val = np.empty(n, np.float32)
+        wts = np.empty(n, np.float32)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_replay_export(self._h, stream, 0, n, states.ctypes.data, None, pol.ctypes.data, last.ctypes.data,
+                                      val.ctypes.data, wts.ctypes.data), "af_replay_export")
+        la = [None if c < 0 else (c // S, c % S) for c in last.tolist()]
+        host.data = list(zip(states.astype("U%d" % stride).tolist(), [p.copy() for p in pol], la, val.tolist(), list(wts)))
+        return host
+
+    def load_records(self, data, data_len, result):
+        """Replace the content with RandomStack records (`data`: 5-tuples carrying state strings) and their episode bookkeeping;
+        black_win / white_win are recounted from `result` as utils.py:50-51 does.  One af_replay_append_states: the strings are
+        decoded on the device, and a malformed one is a ReplayError (the stack is left empty then).  More records than the ring
+        holds is a ReplayError too, before anything is touched: nothing is truncated."""
+        S, n = self.board_size, len(data)
+        cap = self.length + 2 * self._max_T
+        if n > cap:
+            raise ReplayError("%d records do not fit a ring of %d positions (length %d + 2 * max_episode %d)" %
+                              (n, cap, self.length, self._max_T))
+        if sum(data_len) != n or len(result) != len(data_len):
+            raise ReplayError("data_len sums to %d over %d episodes for %d records and %d results" %
+                              (sum(data_len), len(data_len), n, len(result)))
+        stride = int(lib().af_replay_state_stride(self._h))
+        # (a string that does not fit its stride arrives without its NUL, which the device reports)
+        states = np.array([d[0].encode("ascii", "replace") for d in data], "S%d" % stride) if n else np.zeros(0, "S%d" % stride)
+        pol = np.empty((n, S * S), np.float32)
+        for i, d in enumerate(data):
+            pol[i] = np.asarray(d[1], np.float32).reshape(-1)
+        last = np.array([-1 if d[2] is None else d[2][0] * S + d[2][1] for d in data], np.int32)
+        val = np.array([d[3] for d in data], np.float32)
+        wts = np.array([d[4] for d in data], np.float32)
+        self._drop_front(self._size())
+        self.data_len, self.result, self.black_win, self.white_win = [], [], 0, 0
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_replay_append_states(self._h, stream, n, states.ctypes.data, stride, pol.ctypes.data, last.ctypes.data,
+                                             val.ctypes.data, wts.ctypes.data), "af_replay_append_states")
+        self.data_len, self.result = [int(v) for v in data_len], list(result)
+        self.white_win = self.result.count(utils.WHITE_WIN)
+        self.black_win = self.result.count(utils.BLACK_WIN)
+
+    @classmethod
+    def from_host(cls, host_stack, device=0, max_episode=None):
+        """A device stack with the board size, length and content of a utils.RandomStack."""
+        st = cls(host_stack.board_size, host_stack.length, device=device, max_episode=max_episode)
+        st.load_records(host_stack.data, host_stack.data_len, host_stack.result)
+        return st
+
+    def save_pickles(self, s=""):
+        """The reference's three files (utils.py:29-40: data_buffer/data{s}.pkl, data_len{s}.pkl, result{s}.pkl) holding builtins
+        and numpy only, so the reference's own RandomStack.load reads them in a process without this package."""
+        os.makedirs("data_buffer", exist_ok=True)
+        self.to_host().save(s)
+
+    def load_pickles(self, s=""):
+        """utils.py:42-57 into the ring: what save_pickles, utils.RandomStack.save or the reference wrote."""
+        import pickle
+        got = {}
+        for attr, stem in self._FILES:
+            with open(f"data_buffer/{stem}{s}.pkl", "rb") as f:
+                got[attr] = pickle.load(f)
+        self.load_records(got["data"], got["data_len"], got["result"])
 
     def get_data(self, batch_size=1):
         """utils.py:118-146.  Draws: np.random.choice(len, num, replace=False), then per sample

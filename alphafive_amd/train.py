@@ -111,11 +111,73 @@ class Trainer(object):
         tensorbundle.save_bundle(os.path.join(ckpt_dir, name), self.variables())
         tensorbundle.write_checkpoint_state(ckpt_dir, name)
 
+    # ---- optimiser state: what a run needs beyond the bundle to continue as if it had not stopped ----
+    def state_dict(self):
+        """-> dict(params, m, v: {name: float32 array}, t: int), host copies."""
+        host = lambda d: {k: x.detach().cpu().numpy().copy() for k, x in d.items()}
+        return dict(params=host(self.params), m=host(self.m), v=host(self.v), t=int(self.t))
 
-def train_loop(config, engine, net, stack, trainer, steps, log=print):
+    def load_state_dict(self, state):
+        """Put a state_dict() back (in place: the parameter tensors keep their identity).  `m`, `v` and `t` may be missing —
+        a bundle alone — and then stay as they are."""
+        with torch.no_grad():
+            for key, dst in (("params", self.params), ("m", self.m), ("v", self.v)):
+                src = state.get(key)
+                if src is None:
+                    continue
+                for k, x in dst.items():
+                    a = np.asarray(src[k], np.float32)
+                    if tuple(a.shape) != tuple(x.shape):
+                        raise ValueError("%s[%s] has shape %s, expected %s" % (key, k, a.shape, tuple(x.shape)))
+                    x.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        if state.get("t") is not None:
+            self.t = int(state["t"])
+
+    @staticmethod
+    def _sidecar(ckpt_dir, step):
+        return os.path.join(ckpt_dir, "alphaFive-%d.opt.npz" % step)
+
+    def save_state(self, ckpt_dir, step):
+        """Adam's slots and step count as a sidecar alphaFive-<step>.opt.npz beside the bundle save() wrote.  The bundle itself
+        stays what the reference's ResNet.restore expects: variables only (the reference's own checkpoints hold no slots
+        either: its Saver is created before its optimiser)."""
+        os.makedirs(ckpt_dir, exist_ok=True)
+        st = self.state_dict()
+        arrays = {"m/" + k: a for k, a in st["m"].items()}
+        arrays.update({"v/" + k: a for k, a in st["v"].items()})
+        np.savez(self._sidecar(ckpt_dir, step), t=np.int64(st["t"]), **arrays)
+
+    def load_state(self, ckpt_dir, step):
+        """The variables of bundle alphaFive-<step> and the slots of its sidecar."""
+        variables = tensorbundle.load_bundle(os.path.join(ckpt_dir, "alphaFive-%d" % step))
+        with np.load(self._sidecar(ckpt_dir, step)) as z:
+            m = {k[2:]: z[k] for k in z.files if k.startswith("m/")}
+            v = {k[2:]: z[k] for k in z.files if k.startswith("v/")}
+            t = int(z["t"])
+        self.load_state_dict(dict(params=variables, m=m, v=v, t=t))
+
+
+def _save_buffer(stack, step):
+    if hasattr(stack, "save_pickles"):                  # replay.DeviceRandomStack: read out of HBM, same three files
+        stack.save_pickles(step)
+    else:
+        os.makedirs("data_buffer", exist_ok=True)
+        stack.save(step)                                # main.py:75
+
+
+def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step=1, resumable=False, ckpt_every=60):
     """main.py:57-76 with the five gen_data processes replaced by the device batch `engine`
-    (alphafive_amd.engine.SelfPlayEngine): every accepted episode triggers 4 minibatches once the buffer is full."""
-    step = 1
+    (alphafive_amd.engine.SelfPlayEngine): every accepted episode triggers 4 minibatches once the buffer is full.
+
+    Every `ckpt_every` steps the weights are saved as a bundle the reference restores.  With resumable=True each of these is
+    followed by the optimiser sidecar (Trainer.save_state) and the replay buffer (the reference's data_buffer/*.pkl under the
+    current directory, main.py:75), so that resume() can hand back `start_step` for a run that continues this one.
+
+    The self-play engine is not snapshotted.  Its trees are by far the largest state of the loop — at BASELINE configs[1] four
+    edge arrays of 4096 games x 2064 nodes x 128 cells x 4 B, ~17 GB of HBM — and what a restart loses is only the games in
+    flight: 4096 of them, ~17 s of self-play at ~240 episodes/s.  The caller's part: build the resumed run's engine with a
+    `seed` / `first_game_id` the first run did not use, or it replays the same noise streams and plays the same games again."""
+    step = start_step
     on_device = hasattr(stack, "iter_push_packed") and hasattr(engine, "post_episodes_device")
     cap = 256
     while step < steps:
@@ -134,10 +196,38 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print):
                 net.set_variables(trainer.variables())          # the engine's evaluator follows the trainer
                 log("step: %d, xcross_loss: %0.3f, mse: %0.3f, entropy: %0.3f" %
                     (step, metrics["cross_entropy"], metrics["value_loss"], metrics["entropy"]))
-                if step % 60 == 0:
+                if step % ckpt_every == 0:
                     trainer.save(config.ckpt_path, step)
+                    if resumable:
+                        trainer.save_state(config.ckpt_path, step)
+                        _save_buffer(stack, step)
         if on_device:
             # a packed append that found its buffer not to hold what the header said appends nothing and raises a device flag,
             # while the host bookkeeping has already advanced: surface it here, once per hand-off, before the ring is sampled again
             stack.check()
+    return step
+
+
+def resume(config, net, stack, trainer, log=print):
+    """Continue from the newest checkpoint the `checkpoint` file in config.ckpt_path names (main.py:29-34 restore=True): its
+    variables go into `trainer` and `net`, the optimiser sidecar into `trainer` if there is one (if not, Adam starts fresh, as
+    it does in the reference, whose checkpoints hold no slots), the buffer files of that step into `stack` if they exist.
+    Returns the step to pass to train_loop as `start_step`.  The engine starts from empty boards: see train_loop."""
+    prefix = tensorbundle.resolve_checkpoint(config.ckpt_path)
+    ckpt_dir, name = os.path.dirname(prefix), os.path.basename(prefix)
+    step = int(name.rsplit("-", 1)[1])
+    if os.path.exists(Trainer._sidecar(ckpt_dir, step)):
+        trainer.load_state(ckpt_dir, step)
+    else:
+        trainer.load_state_dict(dict(params=tensorbundle.load_bundle(prefix)))
+        log("no optimiser state beside %s: Adam starts fresh" % prefix)
+    net.set_variables(trainer.variables())
+    if all(os.path.exists("data_buffer/%s%d.pkl" % (stem, step)) for stem in ("data", "data_len", "result")):
+        if hasattr(stack, "load_pickles"):
+            stack.load_pickles(step)
+        else:
+            stack.load(step)
+    else:
+        log("no replay buffer saved at step %d: the buffer fills from self-play" % step)
+    log("resumed from %s at step %d" % (prefix, step))
     return step

@@ -11,6 +11,9 @@
  *   device — the positions (a ring of boards int8[C], policies float32[C], last-move cell, value, weight) and
  *           get_data()'s per-sample work (utils.py:127-145): rot90^k + vertical flip of board and policy,
  *           the last_action remap, board_to_inputs' three planes, gathered into the batch tensors.
+ *           It also owns the codec between its int8 boards and the run-length state strings the reference's records carry
+ *           (utils.py:156-196), in both directions: af_replay_export is the way out of the ring (positions in logical order,
+ *           as state strings and/or boards, for RandomStack's data*.pkl), af_replay_append_states the way back in.
  * Results are bit-identical to the host class (pure gathers of fp32 / small-integer data).
  *
  * Plain pointers, int return codes (0 ok / count, <0 error), no exceptions; one handle per GPU.
@@ -30,7 +33,8 @@ typedef struct af_replay af_replay;
 #define AF_REPLAY_ERR_ARG   (-1)
 #define AF_REPLAY_ERR_HIP   (-2)
 #define AF_REPLAY_ERR_FULL  (-3)   /* append beyond capacity: drop from the front first */
-#define AF_REPLAY_ERR_RANGE (-4)   /* sample index / drop count outside the stored range */
+#define AF_REPLAY_ERR_RANGE (-4)   /* sample index / drop count / export range outside the stored range */
+#define AF_REPLAY_ERR_FORMAT (-5)  /* a state string that is not S rows of S cells in utils.py:156-175's alphabet */
 
 /* capacity = most positions ever resident at once (RandomStack.length + the longest episode pushed twice). */
 int af_replay_create(int32_t board_size, int32_t capacity, int32_t device, af_replay** out);
@@ -57,6 +61,25 @@ int af_replay_set_weights(af_replay* r, const float* table_host, int32_t max_T);
 /* AF_REPLAY_ERR_RANGE if a packed append since the last call found the buffer not to hold the episode the host described (it
  * appended nothing then); synchronises `stream`.  AF_REPLAY_OK otherwise. */
 int af_replay_check(af_replay* r, void* stream);
+
+/* Bytes per exported state string: S*(S+1) + 1.  (A row of S cells encodes to at most S characters - stones + runs <= stones +
+ * empties - plus its '/'; one NUL.) */
+int32_t af_replay_state_stride(const af_replay* r);
+/* Read positions first .. first+n-1, counted from the oldest, in order, into HOST arrays shaped as af_replay_append takes them,
+ * plus states char[n][af_replay_state_stride] (utils.py:156-175 board_to_state: per row a run of c empties is 'a'+c, '3' mine,
+ * '1' theirs, '/' ends the row; NUL-terminated and NUL-padded).  `states` or `boards` may be NULL.  One launch on `stream` gathers
+ * the range out of the ring into a contiguous device staging block (the ring's wrap is invisible to the copies) and writes the
+ * strings, ordered behind any af_replay_append_packed still queued on `stream`; the call returns after the copies have landed.
+ * AF_REPLAY_ERR_RANGE if the range is not stored.  The ring is not modified. */
+int af_replay_export(af_replay* r, void* stream, int32_t first, int32_t n, char* states, int8_t* boards, float* policies,
+                     int32_t* last_cell, float* values, float* weights);
+/* af_replay_append for records that carry state strings (what the reference's data*.pkl holds): states char[n][state_stride],
+ * each NUL-terminated inside its stride; one launch decodes them into the ring's int8 boards.  The decoder checks everything it
+ * derives from the text (no NUL inside the stride, a character other than 'a'+1 .. 'a'+S, '1', '3', '/', a row that runs past S
+ * cells or stops short of them, a row count other than S): any bad string makes the whole call append nothing and return
+ * AF_REPLAY_ERR_FORMAT.  Synchronises `stream` like af_replay_append, so it reports directly, not through af_replay_check. */
+int af_replay_append_states(af_replay* r, void* stream, int32_t n, const char* states, int32_t state_stride, const float* policies,
+                            const int32_t* last_cell, const float* values, const float* weights);
 
 /* Forget the n oldest positions (utils.py:103 `del self.data[:beyond]`). */
 int af_replay_drop_front(af_replay* r, int32_t n);
