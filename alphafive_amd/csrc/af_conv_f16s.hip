@@ -1984,7 +1984,32 @@ struct f16s_net {
     float* pfx = nullptr;         // ... and the policy head's K-half hand-over (16 KB)
     char* stash = nullptr;        // 15x15: corner operands of the layer in flight (af_conv_f16s_h15 -> af_corner_f16s), 6 slabs x 512 B per board
     int abl = 0;
+    std::vector<std::pair<const void*, size_t>> wreg;   // weight-derived buffers and their sizes, in f16s_weight_buffer's order
 };
+
+// fragments (64 lanes x 8 halves, hi and lo) of a packed layer / a separately produced projection / the head tensors
+static int layer_frags(const LayerCfg& L) { return (L.cout / 32) * L.KS * ((L.pcin / 32) * (2 / L.KS) + (L.cin / 32) * 9 * (2 / L.KS)); }
+static int proj_frags(const LayerCfg& L, int cout) { return (cout / 32) * L.KS * (L.cin / 32) * (2 / L.KS); }
+constexpr int kStemFrags = 8, kHconvFrags = 2;
+static int vfc_frags(int npix) { return (npix + 3) / 4 * 2; }
+static int pfc_frags(int npix) { return npix * ((npix + 31) / 32); }
+constexpr size_t kFragBytes = 2 * 64 * 16;
+
+// f16s_weight_buffer's order: stem_w, stem_b, stem_wm, w[0..9], pw[4], pw[8], bias[0..9], hcw[0..1], hcb[0..1], hfw[0..1], hfb[0..1], v2w, v2b
+static void fill_wreg(f16s_net* n) {
+    const int npix = n->S * n->S;
+    auto& R = n->wreg;
+    R.clear();
+    R.push_back({n->stem_w, 75 * 32 * 4}); R.push_back({n->stem_b, 32 * 4}); R.push_back({n->stem_wm, kStemFrags * kFragBytes});
+    for (int l = 0; l < 10; ++l) R.push_back({n->w[l], layer_frags(kLayers[l]) * kFragBytes});
+    for (int l = 0; l < 10; ++l) if (kLayers[l].pj == 1) R.push_back({n->pw[l], proj_frags(kLayers[l], kLayers[l + 1].cout) * kFragBytes});
+    for (int l = 0; l < 10; ++l) R.push_back({n->bias[l], (size_t)kLayers[l].cout * 4});
+    for (int h = 0; h < 2; ++h) R.push_back({n->hcw[h], kHconvFrags * kFragBytes});
+    for (int h = 0; h < 2; ++h) R.push_back({n->hcb[h], 64});
+    R.push_back({n->hfw[0], vfc_frags(npix) * kFragBytes}); R.push_back({n->hfw[1], pfc_frags(npix) * kFragBytes});
+    R.push_back({n->hfb[0], 64 * 4}); R.push_back({n->hfb[1], (size_t)npix * 4});
+    R.push_back({n->v2w, 64 * 4}); R.push_back({n->v2b, 4});
+}
 
 int f16s_supported(int board_size) { return board_size == 11 || board_size == 15; }
 
@@ -2128,6 +2153,7 @@ int f16s_create(f16s_net** out, int board_size, int max_batch, int device, const
         if (!rc) FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_fc_f16s<Geo<15>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPfLds));
     }
     if (rc) { f16s_destroy(n); return rc; }
+    fill_wreg(n);
     *out = n;
     return 0;
 }
@@ -2137,6 +2163,219 @@ void f16s_destroy(f16s_net* n) {
     (void)hipSetDevice(n->device);
     for (void* p : n->allocs) (void)hipFree(p);
     delete n;
+}
+
+
+// ------------------------------------------- in-place weight update from device memory -------------------------------------------
+// af_net_update_device: the packers above (pack_layer, pack_proj, pack_frags, the stem) restated write-side, one thread per fragment
+// row (8 halves hi + 8 halves lo = two 16-byte stores), with the same index maps and the same arithmetic — v = w * scale (exact: a
+// power of two), hi = (_Float16)v (nearest even), lo = (_Float16)(v - (float)hi) — so that the bytes equal those of f16s_create.
+// The host packers stay the specification; tests/test_gpu_net_update.py compares the two byte for byte.
+namespace {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+
+struct MaxGroup { const float* a; const float* b; int na, nb; };
+struct MaxTable { MaxGroup g[kF16sScaleGroups]; };
+constexpr int kMaxBlocks = 16;
+
+// max|w| of group blockIdx.y -> out[group] (zeroed before the launch; non-negative floats order as their bit patterns).  A NaN
+// element fails the comparison and does not count, +-inf does: what pick_scale's std::max(mx, std::fabs(v)) does.
+__global__ __launch_bounds__(256) void af_update_absmax(MaxTable T, float* __restrict__ out) {
+    const MaxGroup g = T.g[blockIdx.y];
+    float mx = 0.0f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < g.na + g.nb; i += kMaxBlocks * 256) {
+        const float a = fabsf(i < g.na ? g.a[i] : g.b[i - g.na]);
+        if (a > mx) mx = a;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { const float o = __shfl_xor(mx, off); if (o > mx) mx = o; }
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) if (red[w] > mx) mx = red[w];
+        if (mx > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(out) + blockIdx.y, __float_as_uint(mx));
+    }
+}
+
+enum { FK_LAYER = 0, FK_STEM = 1, FK_HCONV = 2, FK_VFC = 3, FK_PFC = 4 };
+// one packed buffer: kind FK_LAYER = pack_layer (a produced projection is a layer of projection items only: cin = 0, pcin = the
+// producer's cin), w3 HWIO [9][cin][cout], w1 [pcin][cout]; the other kinds read w3 only; nc = couts of a head conv; npix = S*S
+struct FragDesc { uint4* dst; const float* w3; const float* w1; float scale; int kind, frags, cin, cout, pcin, KS, nc, npix; };
+constexpr int kMaxFragBufs = 17;
+struct FragTable { FragDesc d[kMaxFragBufs]; };
+
+__device__ __forceinline__ int dev_row_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }
+
+// element e of lane `lane` of fragment f, scaled; the index maps of pack_layer / the stem loop / the pack_frags callers of f16s_create
+__device__ __forceinline__ float frag_value(const FragDesc& D, int f, int lane, int e) {
+#pragma clang fp contract(off)
+    const int m = lane & 31, kh = lane >> 5;
+    switch (D.kind) {
+        case FK_LAYER: {
+            const int C16 = 2 / D.KS, NSP = D.pcin / 32, NIT = NSP * C16 + (D.cin / 32) * 9 * C16;
+            const int item = f % NIT, tk = f / NIT, ks = tk % D.KS, tile = tk / D.KS;
+            const bool proj = item < NSP * C16;
+            int s, c, tap = 0;
+            if (proj) { s = item / C16; c = item - s * C16; }
+            else { const int it = item - NSP * C16; s = it / (9 * C16); c = (it / 9) % C16; tap = it % 9; }
+            const int c16 = D.KS == 2 ? ks : c;
+            const int co = 32 * tile + dev_row_perm(m), ci = 32 * s + 16 * c16 + 8 * kh + e;
+            return (proj ? D.w1[(size_t)ci * D.cout + co] : D.w3[((size_t)tap * D.cin + ci) * D.cout + co]) * D.scale;
+        }
+        case FK_STEM: {            // [k-step f][lane][8]: k group g = 2f + kh = cin*5 + ky, tap kx = e < 5
+            const int g = 2 * f + kh;
+            if (e >= 5 || g >= 15) return 0.0f;
+            const int cin = g / 5, ky = g - 5 * cin;
+            return D.w3[(size_t)((ky * 5 + e) * 3 + cin) * 32 + dev_row_perm(m)] * D.scale;
+        }
+        case FK_HCONV: {
+            const int co = m < 16 ? 8 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3) : 99, ci = 16 * kh + 8 * f + e;
+            return co < D.nc ? D.w3[(size_t)ci * D.nc + co] * D.scale : 0.0f;
+        }
+        case FK_VFC: {
+            const int s_ = f >> 1, mt = f & 1, px = 4 * s_ + 2 * kh + (e >> 2), ch = e & 3, j = 32 * mt + dev_row_perm(m);
+            return px < D.npix ? D.w3[(size_t)(ch * D.npix + px) * 64 + j] * D.scale : 0.0f;
+        }
+        default: {                 // FK_PFC
+            const int nlt = (D.npix + 31) / 32, px = f / nlt, mt = f - px * nlt, c16 = 8 * kh + e, j = 32 * mt + dev_row_perm(m);
+            return j < D.npix ? D.w3[(size_t)(c16 * D.npix + px) * D.npix + j] * D.scale : 0.0f;
+        }
+    }
+}
+
+constexpr int kFragBlocks = 64;
+// buffer blockIdx.y; a thread per fragment row (fragment f, lane): [f][hi|lo][lane] x 16 bytes
+__global__ __launch_bounds__(256) void af_update_pack_frags(FragTable T) {
+#pragma clang fp contract(off)
+    const FragDesc& D = T.d[blockIdx.y];
+    for (int row = blockIdx.x * 256 + threadIdx.x; row < D.frags * 64; row += kFragBlocks * 256) {
+        const int f = row >> 6, lane = row & 63;
+        h8 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float v = frag_value(D, f, lane, e);
+            const _Float16 h = (_Float16)v;
+            hi[e] = h;
+            lo[e] = (_Float16)(v - (float)h);
+        }
+        h8* dst = reinterpret_cast<h8*>(D.dst);
+        dst[(size_t)(2 * f) * 64 + lane] = hi;
+        dst[(size_t)(2 * f + 1) * 64 + lane] = lo;
+    }
+}
+
+constexpr int kMaxCopies = 48, kCopyBlocks = 32;
+struct CopyTable { UpdCopy d[kMaxCopies]; };
+__global__ __launch_bounds__(256) void af_update_copy(CopyTable T) {
+    const UpdCopy& D = T.d[blockIdx.y];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < D.n_dst; i += kCopyBlocks * 256) {
+        float v = 0.0f;
+        if (i < D.n_src) v = D.sum ? D.a[i] + (D.b ? D.b[i] : 0.0f) : D.a[i];
+        D.dst[i] = v;
+    }
+}
+
+}  // namespace
+
+int upd_launch_copies(hipStream_t st, const UpdCopy* d, int count) {
+    if (count < 1 || count > kMaxCopies) return -1;
+    CopyTable T = {};
+    for (int i = 0; i < count; ++i) T.d[i] = d[i];
+    hipLaunchKernelGGL(af_update_copy, dim3(kCopyBlocks, count), dim3(256), 0, st, T);
+    FS_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// scale groups, in order: 0 stem; 1 + 3b conv1 of block b, 2 + 3b conv2 (+ the folded projection), 3 + 3b the produced projection
+// (computed for every block, used by blocks 3 and 5); 16 / 17 value / policy head conv; 18 value/fc1; 19 policy/fc
+int f16s_update_absmax(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, float* max_dev) {
+    const int npix = n->S * n->S;
+    MaxTable T = {};
+    T.g[0] = {D.at("bone/conv1/kernel"), nullptr, 75 * 32, 0};
+    for (int b = 0; b < 5; ++b) {
+        const std::string s = kBlockNames[b];
+        const LayerCfg &L1 = kLayers[2 * b], &L2 = kLayers[2 * b + 1];
+        const float* kr = D.at(s + "_res/kernel");
+        const int nr = L1.cin * L2.cout;
+        T.g[1 + 3 * b] = {D.at(s + "_conv1/kernel"), nullptr, 9 * L1.cin * L1.cout, 0};
+        T.g[2 + 3 * b] = {D.at(s + "_conv2/kernel"), kr, 9 * L2.cin * L2.cout, L1.pj == 1 ? 0 : nr};
+        T.g[3 + 3 * b] = {kr, nullptr, nr, 0};
+    }
+    T.g[16] = {D.at("value/conv/kernel"), nullptr, 32 * 4, 0};
+    T.g[17] = {D.at("policy/conv/kernel"), nullptr, 32 * 16, 0};
+    T.g[18] = {D.at("value/fc1/kernel"), nullptr, 4 * npix * 64, 0};
+    T.g[19] = {D.at("policy/fc/kernel"), nullptr, 16 * npix * npix, 0};
+    FS_HIP_OK(hipMemsetAsync(max_dev, 0, kF16sScaleGroups * sizeof(float), st));
+    hipLaunchKernelGGL(af_update_absmax, dim3(kMaxBlocks, kF16sScaleGroups), dim3(256), 0, st, T, max_dev);
+    FS_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const float* max_host) {
+    const int npix = n->S * n->S;
+    float sc[kF16sScaleGroups];
+    for (int g = 0; g < kF16sScaleGroups; ++g) sc[g] = pick_scale(std::vector<float>(1, max_host[g]), nullptr);
+    FragTable T = {};
+    int nb = 0;
+    auto frag = [&](uint4* dst, const float* w3, const float* w1, float scale, int kind, int frags, int cin, int cout, int pcin, int KS, int nc) {
+        T.d[nb++] = FragDesc{dst, w3, w1, scale, kind, frags, cin, cout, pcin, KS, nc, npix};
+    };
+    UpdCopy C[kMaxCopies];
+    int ncp = 0;
+    auto copy = [&](float* dst, const float* a, const float* b, int n_dst, int n_src, int sum) { C[ncp++] = UpdCopy{dst, a, b, n_dst, n_src, sum}; };
+    frag(n->stem_wm, D.at("bone/conv1/kernel"), nullptr, sc[0], FK_STEM, kStemFrags, 0, 0, 0, 1, 0);
+    copy(n->stem_w, D.at("bone/conv1/kernel"), nullptr, 75 * 32, 75 * 32, 0);
+    copy(n->stem_b, D.at("bone/conv1/bias"), nullptr, 32, 32, 0);
+    for (int b = 0; b < 5; ++b) {
+        const std::string s = kBlockNames[b];
+        const LayerCfg &L1 = kLayers[2 * b], &L2 = kLayers[2 * b + 1];
+        const float *k1 = D.at(s + "_conv1/kernel"), *k2 = D.at(s + "_conv2/kernel"), *kr = D.at(s + "_res/kernel");
+        frag(n->w[2 * b], k1, nullptr, sc[1 + 3 * b], FK_LAYER, layer_frags(L1), L1.cin, L1.cout, L1.pcin, L1.KS, 0);
+        frag(n->w[2 * b + 1], k2, kr, sc[2 + 3 * b], FK_LAYER, layer_frags(L2), L2.cin, L2.cout, L2.pcin, L2.KS, 0);
+        if (L1.pj == 1) frag(n->pw[2 * b], nullptr, kr, sc[3 + 3 * b], FK_LAYER, proj_frags(L1, L2.cout), 0, L2.cout, L1.cin, L1.KS, 0);
+        copy(n->bias[2 * b], D.at(s + "_conv1/bias"), nullptr, L1.cout, L1.cout, 0);
+        copy(n->bias[2 * b + 1], D.at(s + "_conv2/bias"), D.at(s + "_res/bias"), L2.cout, L2.cout, 1);
+    }
+    frag(n->hcw[0], D.at("value/conv/kernel"), nullptr, sc[16], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 4);
+    frag(n->hcw[1], D.at("policy/conv/kernel"), nullptr, sc[17], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 16);
+    frag(n->hfw[0], D.at("value/fc1/kernel"), nullptr, sc[18], FK_VFC, vfc_frags(npix), 0, 0, 0, 1, 0);
+    frag(n->hfw[1], D.at("policy/fc/kernel"), nullptr, sc[19], FK_PFC, pfc_frags(npix), 0, 0, 0, 1, 0);
+    copy(n->hcb[0], D.at("value/conv/bias"), nullptr, 16, 4, 0);
+    copy(n->hcb[1], D.at("policy/conv/bias"), nullptr, 16, 16, 0);
+    copy(n->hfb[0], D.at("value/fc1/bias"), nullptr, 64, 64, 0);
+    copy(n->hfb[1], D.at("policy/fc/bias"), nullptr, npix, npix, 0);
+    copy(n->v2w, D.at("value/fc2/kernel"), nullptr, 64, 64, 0);
+    copy(n->v2b, D.at("value/fc2/bias"), nullptr, 1, 1, 0);
+    hipLaunchKernelGGL(af_update_pack_frags, dim3(kFragBlocks, nb), dim3(256), 0, st, T);
+    FS_HIP_OK(hipGetLastError());
+    if (upd_launch_copies(st, C, ncp)) return -2;
+    // forwards queued before this call took the old scales by value; later ones take these
+    n->stem_inv_scale = 1.0f / sc[0];
+    for (int b = 0; b < 5; ++b) {
+        n->inv_scale[2 * b] = 1.0f / sc[1 + 3 * b]; n->inv_scale[2 * b + 1] = 1.0f / sc[2 + 3 * b];
+        if (kLayers[2 * b].pj == 1) n->inv_scale_p[2 * b] = 1.0f / sc[3 + 3 * b];
+    }
+    n->hc_inv[0] = 1.0f / sc[16]; n->hc_inv[1] = 1.0f / sc[17];
+    n->hf_inv[0] = 1.0f / sc[18]; n->hf_inv[1] = 1.0f / sc[19];
+    return 0;
+}
+
+int f16s_weight_buffer(const f16s_net* n, int index, const void** ptr, size_t* bytes) {
+    if (!n || index < 0 || index >= (int)n->wreg.size()) return -1;
+    *ptr = n->wreg[index].first; *bytes = n->wreg[index].second;
+    return 0;
+}
+
+// order: stem, inv_scale[0..9], inv_scale_p[0..9] (0 where the layer produces no projection), hc_inv[0..1], hf_inv[0..1]
+int f16s_scales(const f16s_net* n, float* out, int cap) {
+    float v[25];
+    v[0] = n->stem_inv_scale;
+    for (int i = 0; i < 10; ++i) { v[1 + i] = n->inv_scale[i]; v[11 + i] = n->inv_scale_p[i]; }
+    v[21] = n->hc_inv[0]; v[22] = n->hc_inv[1]; v[23] = n->hf_inv[0]; v[24] = n->hf_inv[1];
+    for (int i = 0; i < 25 && i < cap; ++i) out[i] = v[i];
+    return 25;
 }
 
 void f16s_set_ablation(f16s_net* n, int bits) { if (n) n->abl = bits; }

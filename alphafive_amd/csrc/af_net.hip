@@ -610,6 +610,9 @@ struct af_net {
     // activations [max_batch][C][PP]
     float *f0, *g[5], *o[5];
     f16s_net* f16s = nullptr;     // 11x11 boards: the fp16 split-operand convolution path (af_conv_f16s.hip)
+    // af_net_update_device: max|w| per scale group of the split-operand path, device and pinned host (created once, by the first finalize)
+    float *upd_max_dev = nullptr, *upd_max_host = nullptr;
+    std::vector<std::pair<const void*, size_t>> wreg;   // weight-derived buffers of this path, in af_net_debug_weights' order
 };
 
 static int pad32(int c) { return (c + 31) / 32 * 32; }
@@ -657,6 +660,46 @@ static std::vector<float> pack_wino(const std::vector<float>& w, int taps, int c
         }
     return out;
 }
+// pack_wino restated write-side for af_net_update_device: a thread per (cin, cout) pair reads the pair's taps from DEVICE memory and
+// writes its npos values of U = G g G^T: fp64, the same i, j summation order, no contraction, then rounded to fp32 — the bytes of
+// pack_wino (tests/test_gpu_net_update.py compares them).
+struct WinoPackDesc { const float* w; float* out; int taps, cin, cout; };
+constexpr int kWinoBufs = 15, kWinoPackBlocks = 64;
+struct WinoPackTable { WinoPackDesc d[kWinoBufs]; };
+__global__ __launch_bounds__(256) void af_update_pack_wino(WinoPackTable T) {
+#pragma clang fp contract(off)
+    const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const WinoPackDesc& D = T.d[blockIdx.y];
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < D.cin * D.cout; q += kWinoPackBlocks * 256) {
+        const int c = q / D.cout, co = q - c * D.cout;
+        double g[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        if (D.taps == 9) {
+#pragma unroll
+            for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = D.w[((size_t)t * D.cin + c) * D.cout + co];
+        } else {
+            g[1][1] = D.w[(size_t)c * D.cout + co];
+        }
+        float u16[16];
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const int xi = x / 4, nu = x % 4;
+            double u = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) u += G[xi][i] * g[i][j] * G[nu][j];
+            u16[x] = (float)u;
+        }
+        if (D.taps == 9) {
+            float4* o = reinterpret_cast<float4*>(D.out + (size_t)q * 16);       // ((c/2)*2 + (c&1)) * cout + co = q
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = make_float4(u16[4 * r], u16[4 * r + 1], u16[4 * r + 2], u16[4 * r + 3]);
+        } else {
+            *reinterpret_cast<float4*>(D.out + (size_t)q * 4) = make_float4(u16[5], u16[6], u16[9], u16[10]);
+        }
+    }
+}
+
 static std::vector<float> pad_bias(const std::vector<float>& a, const std::vector<float>* b, int cout) {
     std::vector<float> out(pad32(cout), 0.0f);
     for (int i = 0; i < cout; ++i) out[i] = a[i] + (b ? (*b)[i] : 0.0f);
@@ -709,6 +752,8 @@ void af_net_destroy(af_net* n) {
     (void)hipSetDevice(n->device);
     for (void* p : n->allocs) (void)hipFree(p);
     f16s_destroy(n->f16s);
+    if (n->upd_max_dev) (void)hipFree(n->upd_max_dev);
+    if (n->upd_max_host) (void)hipHostFree(n->upd_max_host);
     if (n->branch_stream) (void)hipStreamDestroy(n->branch_stream);
     if (n->ev_trunk) (void)hipEventDestroy(n->ev_trunk);
     if (n->ev_value) (void)hipEventDestroy(n->ev_value);
@@ -765,8 +810,102 @@ int af_net_finalize(af_net* n) {
         NET_HIP_OK(hipEventCreateWithFlags(&n->ev_trunk, hipEventDisableTiming));
         NET_HIP_OK(hipEventCreateWithFlags(&n->ev_value, hipEventDisableTiming));
     }
+    if (!n->upd_max_dev) {       // af_net_update_device allocates nothing: its two small buffers are made here, once per handle
+        NET_HIP_OK(hipMalloc((void**)&n->upd_max_dev, kF16sScaleGroups * sizeof(float)));
+        NET_HIP_OK(hipHostMalloc((void**)&n->upd_max_host, kF16sScaleGroups * sizeof(float), hipHostMallocDefault));
+    }
+    {   // af_net_debug_weights' order on this path (the split-operand path's buffers follow: f16s_weight_buffer)
+        const size_t HW = n->HW;
+        auto& R = n->wreg;
+        R.clear();
+        R.push_back({n->stem_w, 75 * 32 * 4}); R.push_back({n->stem_b, 32 * 4});
+        for (int i = 0; i < 5; ++i) R.push_back({n->conv1_b[i], (size_t)pad32(kBlocks[i].cout) * 4});
+        for (int i = 0; i < 5; ++i) R.push_back({n->sum_b[i], (size_t)pad32(kBlocks[i].cout) * 4});
+        for (int i = 0; i < 5; ++i) R.push_back({n->wino1_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 16 * 4});
+        for (int i = 0; i < 5; ++i) R.push_back({n->wino2_u[i], (size_t)kBlocks[i].cout * kBlocks[i].cout * 16 * 4});
+        for (int i = 0; i < 5; ++i) R.push_back({n->winor_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 4 * 4});
+        R.push_back({n->vc_w, 32 * 4 * 4}); R.push_back({n->vc_b, 4 * 4}); R.push_back({n->v1_w, 4 * HW * 64 * 4});
+        R.push_back({n->v1_b, 64 * 4}); R.push_back({n->v2_w, 64 * 4}); R.push_back({n->v2_b, 4});
+        R.push_back({n->pc_w, 32 * 16 * 4}); R.push_back({n->pc_b, 16 * 4}); R.push_back({n->pf_w, 16 * HW * HW * 4});
+        R.push_back({n->pf_b, HW * 4});
+    }
     n->ready = true;
     return AF_NET_OK;
+}
+
+int af_net_update_device(af_net* n, void* stream, const char* const* tf_names, const float* const* dev_ptrs, const int64_t* counts,
+                         int32_t nvars) {
+    if (!n || !tf_names || !dev_ptrs || !counts) return AF_NET_ERR_ARG;            // (before any HIP call)
+    if (n->allocs.empty()) return AF_NET_ERR_STATE;                                // never finalized: there are no buffers to write into
+    // all or nothing: every name known, every count right, all variables present exactly once — before anything is launched
+    if (nvars != (int32_t)n->expect.size()) return AF_NET_ERR_ARG;
+    f16s_dev_vars D;
+    for (int i = 0; i < nvars; ++i) {
+        if (!tf_names[i] || !dev_ptrs[i]) return AF_NET_ERR_ARG;
+        auto it = n->expect.find(tf_names[i]);
+        if (it == n->expect.end() || (int64_t)it->second != counts[i]) return AF_NET_ERR_NAME;
+        if (!D.emplace(it->first, dev_ptrs[i]).second) return AF_NET_ERR_ARG;      // a name twice (so another one is missing)
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    NET_HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return AF_NET_ERR_STATE;                // this call waits for the stream once: not capturable
+    NET_HIP_OK(hipSetDevice(n->device));
+    if (n->f16s) {
+        // the scales of the split-operand path need max|w| per group: reduced on the device, 80 bytes to the host, ONE wait
+        if (f16s_update_absmax(n->f16s, st, D, n->upd_max_dev)) return AF_NET_ERR_HIP;
+        NET_HIP_OK(hipMemcpyAsync(n->upd_max_host, n->upd_max_dev, kF16sScaleGroups * sizeof(float), hipMemcpyDeviceToHost, st));
+        NET_HIP_OK(hipStreamSynchronize(st));
+        if (f16s_update_pack(n->f16s, st, D, n->upd_max_host)) return AF_NET_ERR_HIP;
+    }
+    WinoPackTable W = {};
+    UpdCopy C[22];
+    int ncp = 0;
+    auto copy = [&](float* dst, const char* a, const float* b, size_t n_dst, int sum) {
+        C[ncp++] = UpdCopy{dst, D.at(a), b, (int)n_dst, (int)n->expect.at(a), sum};
+    };
+    copy(n->stem_w, "bone/conv1/kernel", nullptr, 75 * 32, 0); copy(n->stem_b, "bone/conv1/bias", nullptr, 32, 0);
+    for (int i = 0; i < 5; ++i) {
+        const Block& b = kBlocks[i];
+        const std::string s = b.name;
+        copy(n->conv1_b[i], (s + "_conv1/bias").c_str(), nullptr, pad32(b.cout), 1);          // pad_bias: a + 0.0f
+        copy(n->sum_b[i], (s + "_conv2/bias").c_str(), D.at(s + "_res/bias"), pad32(b.cout), 1);
+        W.d[3 * i] = WinoPackDesc{D.at(s + "_conv1/kernel"), n->wino1_u[i], 9, b.cin, b.cout};
+        W.d[3 * i + 1] = WinoPackDesc{D.at(s + "_conv2/kernel"), n->wino2_u[i], 9, b.cout, b.cout};
+        W.d[3 * i + 2] = WinoPackDesc{D.at(s + "_res/kernel"), n->winor_u[i], 1, b.cin, b.cout};
+    }
+    const size_t HW = n->HW;
+    copy(n->vc_w, "value/conv/kernel", nullptr, 32 * 4, 0); copy(n->vc_b, "value/conv/bias", nullptr, 4, 0);
+    copy(n->v1_w, "value/fc1/kernel", nullptr, 4 * HW * 64, 0); copy(n->v1_b, "value/fc1/bias", nullptr, 64, 0);
+    copy(n->v2_w, "value/fc2/kernel", nullptr, 64, 0); copy(n->v2_b, "value/fc2/bias", nullptr, 1, 0);
+    copy(n->pc_w, "policy/conv/kernel", nullptr, 32 * 16, 0); copy(n->pc_b, "policy/conv/bias", nullptr, 16, 0);
+    copy(n->pf_w, "policy/fc/kernel", nullptr, 16 * HW * HW, 0); copy(n->pf_b, "policy/fc/bias", nullptr, HW, 0);
+    hipLaunchKernelGGL(af_update_pack_wino, dim3(kWinoPackBlocks, kWinoBufs), dim3(256), 0, st, W);
+    NET_HIP_OK(hipGetLastError());
+    if (upd_launch_copies(st, C, ncp)) return AF_NET_ERR_HIP;
+    n->vars.clear();             // the host copy is stale: af_net_finalize needs all 42 variables set again
+    n->ready = true;
+    return AF_NET_OK;
+}
+
+int64_t af_net_debug_weights(af_net* n, int32_t index, void* host_out, int64_t cap_bytes) {
+    if (!n || index < 0 || n->allocs.empty()) return AF_NET_ERR_ARG;
+    const void* p = nullptr;
+    size_t bytes = 0;
+    const int n32 = (int)n->wreg.size();
+    if (index < n32) { p = n->wreg[index].first; bytes = n->wreg[index].second; }
+    else if (!n->f16s || f16s_weight_buffer(n->f16s, index - n32, &p, &bytes)) return AF_NET_ERR_ARG;
+    if (!host_out) return (int64_t)bytes;
+    if (cap_bytes < (int64_t)bytes) return AF_NET_ERR_ARG;
+    NET_HIP_OK(hipSetDevice(n->device));
+    NET_HIP_OK(hipDeviceSynchronize());
+    NET_HIP_OK(hipMemcpy(host_out, p, bytes, hipMemcpyDeviceToHost));
+    return (int64_t)bytes;
+}
+
+int32_t af_net_debug_scales(af_net* n, float* host_out, int32_t cap) {
+    if (!n || !host_out || cap < 0) return AF_NET_ERR_ARG;
+    return n->f16s ? f16s_scales(n->f16s, host_out, cap) : 0;
 }
 
 }  // extern "C"

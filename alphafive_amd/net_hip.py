@@ -32,6 +32,11 @@ def lib():
         L.af_net_set_variable.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
         L.af_net_finalize.argtypes = [vp]
         L.af_net_forward.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
+        L.af_net_update_device.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_int64), C.c_int32]
+        L.af_net_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
+        L.af_net_debug_weights.restype = C.c_int64
+        L.af_net_debug_scales.argtypes = [vp, C.POINTER(C.c_float), C.c_int32]
+        L.af_net_debug_scales.restype = C.c_int32
         L.af_net_flops_per_position.argtypes = [vp]
         L.af_net_flops_per_position.restype = C.c_int64
         L.af_net_small_forward_error.argtypes = [vp]
@@ -70,8 +75,47 @@ class HipNet(object):
         _check(lib().af_net_finalize(self._h), "af_net_finalize")
         self._version += 1
 
+    def load_device(self, tensors):
+        """Weight update without the host (af_net_update_device): `tensors` maps every variable name to a contiguous float32
+        tensor on this handle's device (TF layout); kernels re-pack them in place into the buffers the handle owns, on the
+        current stream, behind the forwards already queued there.  No device-wide wait: the library waits once, for that
+        stream, to learn the weight scales.  Not inside a stream capture (raises NetError).  The tensors must not change before
+        the pack kernels have run — a producer on the same stream is ordered, anything else hands over a snapshot."""
+        names, ptrs, counts = [], [], []
+        for name, t in tensors.items():
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise NetError(f"load_device({name}): a contiguous float32 tensor on {self.device} is required")
+            if t.device.index != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
+                raise NetError(f"load_device({name}): tensor on {t.device}, handle on {self.device}")
+            names.append(name.encode())
+            ptrs.append(t.data_ptr())
+            counts.append(t.numel())
+        n = len(names)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_net_update_device(self._h, stream, (C.c_char_p * n)(*names), (C.c_void_p * n)(*ptrs), (C.c_int64 * n)(*counts), n),
+               "af_net_update_device")
+        self._version += 1
+
+    def debug_weights(self):
+        """Tests: every weight-derived device buffer of the handle as bytes, in af_net_debug_weights' order (synchronises)."""
+        out = []
+        while True:
+            size = lib().af_net_debug_weights(self._h, len(out), None, 0)
+            if size < 0:
+                return out
+            buf = np.empty(size, np.uint8)
+            _check(lib().af_net_debug_weights(self._h, len(out), buf.ctypes.data_as(C.c_void_p), size), "af_net_debug_weights")
+            out.append(buf)
+
+    def debug_scales(self):
+        """Tests: the inverse weight scales of the split-operand path (af_net_debug_scales); empty without that path."""
+        buf = np.zeros(64, np.float32)
+        n = lib().af_net_debug_scales(self._h, buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size)
+        _check(n, "af_net_debug_scales")
+        return buf[:n].copy()
+
     def weights_version(self):
-        """Count of load() calls: what a captured graph over this handle (SelfPlayEngine.run_ticks_graph) is keyed on."""
+        """Count of load() and load_device() calls: what a captured graph over this handle (SelfPlayEngine.run_ticks_graph) is keyed on."""
         return self._version
 
     def bind_outputs(self, policy, value):
@@ -120,8 +164,18 @@ def make_eval(resnet):
             if state["out"] is not None and state["out"][0].shape[0] >= B:
                 state["net"].bind_outputs(*state["out"])
         elif state["version"] != getattr(resnet, "version", None):
-            state["net"].load(resnet.variables)          # set_variables / restore / load_npz since the last call (a weight update)
-            state["version"] = getattr(resnet, "version", None)
+            version = getattr(resnet, "version", None)   # (read before the weights: a newer update shows as one more change next call)
+            snap = resnet.device_snapshot() if hasattr(resnet, "device_snapshot") else None
+            if snap is not None:                         # set_variables_device: the weights are on the device, and stay there
+                tensors, event = snap
+                stream = torch.cuda.current_stream(resnet.device)
+                stream.wait_event(event)
+                state["net"].load_device(tensors)
+                for t in tensors.values():               # the snapshot may be dropped by the next update while this stream still reads it
+                    t.record_stream(stream)
+            else:
+                state["net"].load(resnet.variables)      # set_variables / restore / load_npz since the last call (a weight update)
+            state["version"] = version
         return state["net"](planes)
 
     def bind_outputs(policy, value):

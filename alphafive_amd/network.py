@@ -80,7 +80,8 @@ class ResNet(object):
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
         self.api = None
-        self.variables = {}
+        self._variables = {}
+        self._dev_snap = None                    # set_variables_device: ({name: device tensor}, event) while the host copy is stale
         self._t = {}
         import threading
         # eval_device(): one hand-written-kernel evaluator (packed weights + activation buffers for that thread's largest
@@ -93,6 +94,21 @@ class ResNet(object):
         self.set_variables(random_variables(board_size, seed))
 
     # ---- weights ----
+    @property
+    def variables(self):
+        """{name: float32 array, TF layout} on the host.  After set_variables_device the arrays are made here, on first access."""
+        v = self._variables
+        if v is None:
+            tensors, event = self._dev_snap
+            event.synchronize()
+            v = {k: t.cpu().numpy() for k, t in tensors.items()}
+            self._variables = v
+        return v
+
+    @variables.setter
+    def variables(self, value):
+        self._variables = value
+
     def set_variables(self, variables):
         shapes = variable_shapes(self.board_size)
         for name, shape in shapes.items():
@@ -108,7 +124,40 @@ class ResNet(object):
                 tv = tv.permute(3, 2, 0, 1).contiguous()          # HWIO -> OIHW
             t[k] = tv.to(self.device)
         self._t = t
+        self._dev_snap = None
         self.version = getattr(self, "version", 0) + 1      # evaluators built from an older weight set reload (net_hip.make_eval)
+
+    def set_variables_device(self, tensors):
+        """set_variables from torch tensors without a host copy: `tensors` maps every variable name to a float32 tensor in TF
+        layout (a Trainer's parameters: train.Trainer.device_variables()).  A cuda net takes a device snapshot (clone: the
+        caller may go on writing into its tensors) on the current stream and records an event behind it; the hand-written
+        kernels' evaluators re-pack from that snapshot on the device the next time they are called (net_hip.make_eval ->
+        HipNet.load_device), eval_torch uses it as it is, and .variables / save_npz materialise host arrays on first access.
+        A cpu net does what set_variables does with the tensors' values."""
+        shapes = variable_shapes(self.board_size)
+        for name, shape in shapes.items():
+            if name not in tensors:
+                raise KeyError("missing variable %s" % name)
+            if tuple(tensors[name].shape) != shape:
+                raise ValueError("variable %s has shape %s, expected %s" % (name, tuple(tensors[name].shape), shape))
+        if self.device.type != "cuda":
+            self.set_variables({k: tensors[k].detach().cpu().numpy() for k in shapes})
+            return
+        with torch.no_grad():
+            snap = {k: tensors[k].detach().to(device=self.device, dtype=torch.float32).clone(memory_format=torch.contiguous_format)
+                    for k in shapes}
+            t = {k: (v.permute(3, 2, 0, 1).contiguous() if v.dim() == 4 else v) for k, v in snap.items()}     # HWIO -> OIHW
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self.device))
+        self._dev_snap = (snap, event)
+        self._variables = None                   # stale: rebuilt from the snapshot when somebody reads .variables
+        self._t = t
+        self.version = getattr(self, "version", 0) + 1
+
+    def device_snapshot(self):
+        """-> ({name: device tensor}, event recorded behind their last write) if the current weights came from
+        set_variables_device, else None (net_hip.make_eval decides between HipNet.load_device and HipNet.load with it)."""
+        return self._dev_snap
 
     def restore(self, ckpt_path):
         """network.py:113-122: directory with a `checkpoint` file or a checkpoint prefix."""

@@ -104,6 +104,11 @@ class Trainer(object):
     def variables(self):
         return {k: p.detach().cpu().numpy().copy() for k, p in self.params.items()}
 
+    def device_variables(self):
+        """{name: parameter tensor, detached} on the trainer's device: no copy — the tensors the next step() writes into
+        (ResNet.set_variables_device takes its own snapshot)."""
+        return {k: p.detach() for k, p in self.params.items()}
+
     def save(self, ckpt_dir, step):
         """main.py:73-74 — a checkpoint the reference's ResNet.restore() can load."""
         os.makedirs(ckpt_dir, exist_ok=True)
@@ -165,7 +170,8 @@ def _save_buffer(stack, step):
         stack.save(step)                                # main.py:75
 
 
-def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step=1, resumable=False, ckpt_every=60):
+def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step=1, resumable=False, ckpt_every=60,
+               weights_on_device=False):
     """main.py:57-76 with the five gen_data processes replaced by the device batch `engine`
     (alphafive_amd.engine.SelfPlayEngine): every accepted episode triggers 4 minibatches once the buffer is full.
 
@@ -176,7 +182,11 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step
     The self-play engine is not snapshotted.  Its trees are by far the largest state of the loop — at BASELINE configs[1] four
     edge arrays of 4096 games x 2064 nodes x 128 cells x 4 B, ~17 GB of HBM — and what a restart loses is only the games in
     flight: 4096 of them, ~17 s of self-play at ~240 episodes/s.  The caller's part: build the resumed run's engine with a
-    `seed` / `first_game_id` the first run did not use, or it replays the same noise streams and plays the same games again."""
+    `seed` / `first_game_id` the first run did not use, or it replays the same noise streams and plays the same games again.
+
+    weights_on_device=True hands the new weights to the engine's evaluator without the host: net.set_variables_device(
+    trainer.device_variables()) snapshots the parameters on the device and the evaluator re-packs them in place
+    (af_net_update_device) instead of 42 device-to-host copies, a host re-pack and a reallocation of the evaluator per step."""
     step = start_step
     on_device = hasattr(stack, "iter_push_packed") and hasattr(engine, "post_episodes_device")
     cap = 256
@@ -193,7 +203,10 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step
                     boards, weights, values, policies = stack.get_data(batch_size=config.batch_size)
                     metrics = trainer.step(boards, weights, values, policies, config.get_lr(step), metrics=i == 3)
                 step += 1
-                net.set_variables(trainer.variables())          # the engine's evaluator follows the trainer
+                if weights_on_device:                           # the engine's evaluator follows the trainer
+                    net.set_variables_device(trainer.device_variables())
+                else:
+                    net.set_variables(trainer.variables())
                 log("step: %d, xcross_loss: %0.3f, mse: %0.3f, entropy: %0.3f" %
                     (step, metrics["cross_entropy"], metrics["value_loss"], metrics["entropy"]))
                 if step % ckpt_every == 0:

@@ -37,6 +37,25 @@ int af_net_set_variable(af_net* n, const char* tf_name, const float* host_data, 
 /* Repack (k-pair-major streams for the MFMA kernels) and upload; call after all 42 variables are set. */
 int af_net_finalize(af_net* n);
 
+/* Weight hand-over without the host: all 42 variables at once, from DEVICE memory (fp32, TF layout, same names / counts as
+ * af_net_set_variable), re-packed by kernels IN PLACE into the buffers the handle already owns — nothing is freed, nothing is
+ * allocated, no weight is copied to the host.  Every weight-derived buffer of BOTH conv paths is rewritten (af_net_tune(0, .) may
+ * switch paths at any time), to the bytes af_net_set_variable + af_net_finalize make of the same values.
+ *   - the handle must have been finalized once (AF_NET_ERR_STATE otherwise);
+ *   - all or nothing: names, counts and "each of the 42 exactly once" are checked before anything is launched — an unknown name or a
+ *     wrong count returns AF_NET_ERR_NAME; a null handle / array / entry, nvars != 42 or a name given twice AF_NET_ERR_ARG (null
+ *     handle or arrays: before any HIP call);
+ *   - stream-ordered on `stream`: after the forwards already queued there, before later ones.  ONE host wait: the split-operand
+ *     path's power-of-two scales depend on max|w| per scale group and the forward kernels take them by value, so the call reduces
+ *     the maxima on the device, copies 80 bytes to pinned memory, synchronises `stream` once, picks the scales on the host and
+ *     launches the pack kernels; everything else is asynchronous.  The source tensors must stay unchanged until the pack kernels have
+ *     run (stream order suffices for a producer on the same stream);
+ *   - because it synchronises, it must not be called while `stream` is being captured: AF_NET_ERR_STATE, nothing launched;
+ *   - afterwards the handle's host copy of the variables is gone: af_net_finalize returns AF_NET_ERR_STATE until all 42 have been
+ *     set again with af_net_set_variable. */
+int af_net_update_device(af_net* n, void* stream, const char* const* tf_names, const float* const* dev_ptrs, const int64_t* counts,
+                         int32_t nvars);
+
 /* planes_dev float32[batch][3][S][S] (utils.py:256 board_to_inputs layout) ->
  * policy_dev float32[batch][S*S] (softmax probabilities), value_dev float32[batch].
  * Asynchronous on `stream` (hipStream_t; NULL = default stream). */
@@ -64,6 +83,22 @@ int af_net_tune(int32_t key, int32_t value);
  * (0 stem, 1/2 block1 conv1/output, 3/4 block2, 5 block3 conv1, 6/7 block4, 8 block5 conv1) of the first `batch`
  * positions of the last forward, as fp32 [batch][C][121] on the host.  Returns the channel count C or <0. */
 int af_net_debug_activation(af_net* n, int32_t which, int32_t batch, float* host_out);
+
+/* Tests: weight-derived device buffer `index` copied to host_out (cap_bytes must hold it); returns its size in bytes (also when
+ * host_out is NULL), AF_NET_ERR_ARG past the last index.  Synchronises the device.  Order, blocks b = 0..4 (bone/block1, bone/block2,
+ * value/block3, policy/block4, policy/block5), layers l = 2b (conv1), 2b+1 (conv2):
+ *   fp32 Winograd path, every board size — 0 stem kernel, 1 stem bias, 2+b conv1 bias (padded), 7+b conv2 + res bias (padded),
+ *     12+b / 17+b / 22+b Winograd-domain conv1 / conv2 / projection kernels, 27..36 value/conv kernel, bias, value/fc1 kernel, bias,
+ *     value/fc2 kernel, bias, policy/conv kernel, bias, policy/fc kernel, bias;
+ *   fp16 split-operand path, 11x11 and 15x15 boards only — 37 stem kernel, 38 stem bias, 39 stem A fragments, 40+l layer A fragments,
+ *     50 / 51 produced projection of value/block3 / policy/block5, 52+l layer bias (odd l: conv2 + res), 62 / 63 value / policy head
+ *     conv fragments, 64 / 65 their padded biases, 66 / 67 value/fc1 / policy/fc fragments, 68 / 69 their biases, 70 value/fc2
+ *     kernel, 71 value/fc2 bias. */
+int64_t af_net_debug_weights(af_net* n, int32_t index, void* host_out, int64_t cap_bytes);
+/* Tests: the inverse weight scales the split-operand forward passes by value — stem, layers 0..9, produced projections by producer
+ * layer 0..9 (0 where there is none), value / policy head conv, value/fc1, policy/fc: 25 floats; returns how many there are (0 on a
+ * board size without that path), writes min(cap, that) of them. */
+int32_t af_net_debug_scales(af_net* n, float* host_out, int32_t cap);
 
 /* Batches of at most 8 positions on 11x11 (what genData/player.py:186-202 asks for: one leaf per simulation) run as ONE launch of
  * dataflow roles + the policy head's dense layer (csrc/af_conv_f16s.hip: af_small_forward_f16s; af_net_tune(7, 2048) = the nine
