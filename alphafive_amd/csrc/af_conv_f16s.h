@@ -7,15 +7,14 @@
 
 #include <map>
 #include <string>
-#include <vector>
 
 struct f16s_net;
 
-// variables under their checkpoint names in TF layout (as af_net_set_variable received them); board sizes 11 (one pseudo-position
-// per board) and 15 (two half-board pseudo-positions per board); on both the heads are fused (the 1x1 head convolutions ride the last conv
-// of each branch, the dense layers run on af_value_fc_f16s / af_policy_fc_f16s<Geo<S>>)
+// board sizes 11 (one pseudo-position per board) and 15 (two half-board pseudo-positions per board); on both the heads are fused (the
+// 1x1 head convolutions ride the last conv of each branch, the dense layers run on af_value_fc_f16s / af_policy_fc_f16s<Geo<S>>)
 int f16s_supported(int board_size);
-int f16s_create(f16s_net** out, int board_size, int max_batch, int device, const std::map<std::string, std::vector<float>>& vars);
+// allocates every device buffer of the handle; the weight-derived ones hold nothing until the first f16s_update_pack
+int f16s_create(f16s_net** out, int board_size, int max_batch, int device);
 void f16s_destroy(f16s_net* n);
 // stem + bone/block1 + bone/block2 on stream st
 int f16s_trunk(f16s_net* n, hipStream_t st, const float* planes_dev, int batch);
@@ -34,19 +33,21 @@ int f16s_small_forward_error(f16s_net* n);                         // 1 if a rol
 void f16s_set_ablation(f16s_net* n, int bits);
 int f16s_read_activation(f16s_net* n, int which, int batch, float* host);
 
-// ---- in-place weight update from device memory (af_net_update_device) ----
+// ---- weight packing, from device memory and in place: the one packer of this path (af_net_finalize over the variables it staged,
+// af_net_update_device over the caller's tensors) ----
 // name -> fp32 TF-layout tensor in DEVICE memory, all 42 variables (af_net.hip has checked names and counts)
 typedef std::map<std::string, const float*> f16s_dev_vars;
 constexpr int kF16sScaleGroups = 20;       // stem | per block: conv1, conv2 (+ folded projection), produced projection | 2 head convs | value/fc1 | policy/fc
 // max|w| of every scale group -> max_dev[kF16sScaleGroups] (device; NaN elements do not count), asynchronous on st
 int f16s_update_absmax(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, float* max_dev);
-// re-pack every weight-derived buffer of the split-operand path in place from D with pick_scale(max_host[group]), asynchronous on
-// st, and store the new inverse scales in the handle; max_host = what f16s_update_absmax produced, already on the host
+// pack every weight-derived buffer of the split-operand path in place from D, each scale group with the power-of-two scale its
+// max_host[group] picks, asynchronous on st, and store the new inverse scales in the handle; max_host = what f16s_update_absmax
+// produced, already on the host
 int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const float* max_host);
 // weight-derived device buffers in a fixed order (af_net_debug_weights): 0 on success, -1 past the last one
 int f16s_weight_buffer(const f16s_net* n, int index, const void** ptr, size_t* bytes);
 int f16s_scales(const f16s_net* n, float* out, int cap);           // the 25 inverse scales (af_net_debug_scales); returns how many
-// elementwise device copies shared by both paths' updates: dst[i] = i < n_src ? (sum ? a[i] + (b ? b[i] : 0.0f) : a[i]) : 0.0f, i < n_dst
+// elementwise device copies shared by both paths' packing: dst[i] = i < n_src ? (sum ? a[i] + (b ? b[i] : 0.0f) : a[i]) : 0.0f, i < n_dst
 struct UpdCopy { float* dst; const float* a; const float* b; int n_dst, n_src, sum; };
 int upd_launch_copies(hipStream_t st, const UpdCopy* d, int count);
 

@@ -427,7 +427,7 @@ __device__ __forceinline__ void f16s_body(const F16sArgs& A, char* smem, const i
     h8 HA[HDS > 0 ? 4 : 1];
     float hb[HDS > 0 ? 8 : 1];
     if (FU > 0) {
-        // the second convolution's A fragments -> LDS ([item][hi|lo][64 lanes] x 16 bytes, pack_layer's order), its bias -> registers
+        // the second convolution's A fragments -> LDS ([item][hi|lo][64 lanes] x 16 bytes, the packed layer's item order), its bias -> registers
         const uint4* w2 = A.w2;
 #pragma unroll
         for (int i = 0; i < 9; ++i) *reinterpret_cast<uint4*>(smem + kW2Off + (uint32_t)(i * 256 + (int)threadIdx.x) * 16u) = w2[i * 256 + threadIdx.x];
@@ -1000,7 +1000,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 // one 16-byte unit of ITS board, read from the compact copy the half-1 workgroups of af_conv_f16s_h15 made while the slab was in LDS
 // (512 contiguous bytes per slab and board: 9 MB per layer and 4096 boards, L2 / Infinity-Cache resident; straight from the S32 tensor
 // the same units cost three 128-byte lines per 64 useful bytes = 50 MB and 25-45 us per launch: profiles/r5_09); the A fragments are
-// the layer's own packed weights (pack_layer: [cout tile][ks][item][hi|lo]).
+// the layer's own packed weights (FK_LAYER: [cout tile][ks][item][hi|lo]).
 // A workgroup = 32 boards x up to 4 cout tiles (one per wave).
 // BIT-IDENTICAL to what the two-halves launch (af_conv_f16s on half 1, tile 3, lane 0) computes for this pixel — small batches still
 // take that launch, and a board's result must not depend on the batch it is evaluated in: the same MFMAs on the same operands in the
@@ -1761,103 +1761,6 @@ const LayerCfg kLayers[10] = {
 };
 const char* const kBlockNames[5] = {"bone/block1", "bone/block2", "value/block3", "policy/block4", "policy/block5"};
 
-template <class T>
-int dev_upload(std::vector<void*>& allocs, T** dst, const void* src, size_t bytes) {
-    void* q = nullptr;
-    FS_HIP_OK(hipMalloc(&q, bytes));
-    FS_HIP_OK(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice));
-    allocs.push_back(q);
-    *dst = (T*)q;
-    return 0;
-}
-
-// A fragments of one layer: [cout tile][ks][item][hi|lo][lane][8]; item order = the kernel's consumption order
-// (projection slabs first; per slab: 16-channel k-step c, then the 9 taps); MFMA row m of a tile holds cout
-// 32*tile + 16*((m>>2)&1) + 8*(m>>4) + 4*((m>>3)&1) + (m&3) so that a lane's 16 accumulator rows are consecutive couts.
-// w3: HWIO [9][cin][cout]; w1: [pcin][cout] or null.
-std::vector<_Float16> pack_layer(const LayerCfg& L, const float* w3, const float* w1, float scale) {
-    const int NSM = L.cin / 32, NSP = L.pcin / 32, C16 = 2 / L.KS;
-    const int NIT = NSP * C16 + NSM * 9 * C16, tiles = L.cout / 32;
-    std::vector<_Float16> out((size_t)tiles * L.KS * 2 * NIT * 64 * 8);
-    for (int tile = 0; tile < tiles; ++tile)
-        for (int ks = 0; ks < L.KS; ++ks) {
-            int item = 0;
-            for (int j = 0; j < NSP + NSM; ++j) {
-                const bool proj = j < NSP;
-                const int s = proj ? j : j - NSP;
-                for (int c = 0; c < C16; ++c)
-                    for (int tap = 0; tap < (proj ? 1 : 9); ++tap, ++item) {
-                        const int c16 = L.KS == 2 ? ks : c;
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int m = lane & 31;
-                                const int co = 32 * tile + 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3);
-                                const int ci = 32 * s + 16 * c16 + 8 * (lane >> 5) + e;
-                                const float v = (proj ? w1[(size_t)ci * L.cout + co] : w3[((size_t)tap * L.cin + ci) * L.cout + co]) * scale;
-                                const _Float16 h = (_Float16)v;
-                                const size_t base = ((((size_t)(tile * L.KS + ks) * NIT + item) * 2) * 64 + lane) * 8 + e;
-                                out[base] = h;
-                                out[base + 64 * 8] = (_Float16)(v - (float)h);
-                            }
-                    }
-            }
-        }
-    return out;
-}
-
-// A fragments of a separately produced 1x1 projection (producer layer L: its own cin -> `cout` couts): [cout tile][ks][item]
-// [hi|lo][lane][8], one item per (slab, 16-channel k-step), in the producer's order.  w1: [cin][cout].
-std::vector<_Float16> pack_proj(const LayerCfg& L, int cout, const float* w1, float scale) {
-    const int NSM = L.cin / 32, C16 = 2 / L.KS, NPW = NSM * C16, tiles = cout / 32;
-    std::vector<_Float16> out((size_t)tiles * L.KS * 2 * NPW * 64 * 8);
-    for (int tile = 0; tile < tiles; ++tile)
-        for (int ks = 0; ks < L.KS; ++ks)
-            for (int s = 0; s < NSM; ++s)
-                for (int c = 0; c < C16; ++c) {
-                    const int item = s * C16 + c, c16 = L.KS == 2 ? ks : c;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int m = lane & 31;
-                            const int co = 32 * tile + 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3);
-                            const int ci = 32 * s + 16 * c16 + 8 * (lane >> 5) + e;
-                            const float v = w1[(size_t)ci * cout + co] * scale;
-                            const _Float16 h = (_Float16)v;
-                            const size_t base = ((((size_t)(tile * L.KS + ks) * NPW + item) * 2) * 64 + lane) * 8 + e;
-                            out[base] = h;
-                            out[base + 64 * 8] = (_Float16)(v - (float)h);
-                        }
-                }
-    return out;
-}
-
-float pick_scale(const std::vector<float>& a, const std::vector<float>* b) {
-    float mx = 0.0f;
-    for (float v : a) mx = std::max(mx, std::fabs(v));
-    if (b) for (float v : *b) mx = std::max(mx, std::fabs(v));
-    if (!(mx > 0.0f) || !std::isfinite(mx)) return 1.0f;
-    int e;
-    std::frexp(mx, &e);                     // mx = f * 2^e, f in [0.5, 1)
-    return std::ldexp(1.0f, 13 - e);        // mx * scale in [4096, 8192): 8x below the fp16 maximum
-}
-
-
-// MFMA row m of a 32-row tile -> the output it carries, such that a lane's 16 accumulator rows are 16 consecutive outputs
-inline int row_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }
-
-template <class F>
-std::vector<_Float16> pack_frags(int nfrag, F&& val) {          // [fragment][hi|lo][lane][8], val(fragment, lane, e) already scaled
-    std::vector<_Float16> out((size_t)nfrag * 2 * 64 * 8);
-    for (int f = 0; f < nfrag; ++f)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 8; ++e) {
-                const float v = val(f, lane, e);
-                const _Float16 h = (_Float16)v;
-                out[(((size_t)f * 2 + 0) * 64 + lane) * 8 + e] = h;
-                out[(((size_t)f * 2 + 1) * 64 + lane) * 8 + e] = (_Float16)(v - (float)h);
-            }
-    return out;
-}
-
 constexpr int kSmallBatch = 8;             // <= this many positions: a position's pixel tiles are split over workgroups (af_conv_f16s_sb)
 template <class G, int NSM, int NSP, int CT, int KS, int PS, bool OUT32, bool XACC, int PJ = 0, int HD = 0, int DIST = kDist, int WPE = 1>
 int launch_cfg(hipStream_t st, const F16sArgs& a, int gy, int ncu) {
@@ -1995,165 +1898,66 @@ static int vfc_frags(int npix) { return (npix + 3) / 4 * 2; }
 static int pfc_frags(int npix) { return npix * ((npix + 31) / 32); }
 constexpr size_t kFragBytes = 2 * 64 * 16;
 
-// f16s_weight_buffer's order: stem_w, stem_b, stem_wm, w[0..9], pw[4], pw[8], bias[0..9], hcw[0..1], hcb[0..1], hfw[0..1], hfb[0..1], v2w, v2b
-static void fill_wreg(f16s_net* n) {
-    const int npix = n->S * n->S;
-    auto& R = n->wreg;
-    R.clear();
-    R.push_back({n->stem_w, 75 * 32 * 4}); R.push_back({n->stem_b, 32 * 4}); R.push_back({n->stem_wm, kStemFrags * kFragBytes});
-    for (int l = 0; l < 10; ++l) R.push_back({n->w[l], layer_frags(kLayers[l]) * kFragBytes});
-    for (int l = 0; l < 10; ++l) if (kLayers[l].pj == 1) R.push_back({n->pw[l], proj_frags(kLayers[l], kLayers[l + 1].cout) * kFragBytes});
-    for (int l = 0; l < 10; ++l) R.push_back({n->bias[l], (size_t)kLayers[l].cout * 4});
-    for (int h = 0; h < 2; ++h) R.push_back({n->hcw[h], kHconvFrags * kFragBytes});
-    for (int h = 0; h < 2; ++h) R.push_back({n->hcb[h], 64});
-    R.push_back({n->hfw[0], vfc_frags(npix) * kFragBytes}); R.push_back({n->hfw[1], pfc_frags(npix) * kFragBytes});
-    R.push_back({n->hfb[0], 64 * 4}); R.push_back({n->hfb[1], (size_t)npix * 4});
-    R.push_back({n->v2w, 64 * 4}); R.push_back({n->v2b, 4});
-}
-
 int f16s_supported(int board_size) { return board_size == 11 || board_size == 15; }
 
-int f16s_create(f16s_net** out, int board_size, int max_batch, int device, const std::map<std::string, std::vector<float>>& V) {
+template <class T>
+static int dev_alloc(f16s_net* n, T** dst, size_t bytes, bool zero) {
+    void* q = nullptr;
+    FS_HIP_OK(hipMalloc(&q, bytes));
+    n->allocs.push_back(q);
+    if (zero) FS_HIP_OK(hipMemset(q, 0, bytes));
+    *dst = (T*)q;
+    return 0;
+}
+
+// Picks the geometry and allocates every device buffer of the handle; it packs nothing.  The weight-derived buffers are filled, and
+// the inverse scales set, by f16s_update_pack (af_net_finalize runs it over the staged variables before any forward).  wbuf registers
+// each weight-derived buffer for f16s_weight_buffer as it allocates it, so what is allocated and what is reported cannot differ:
+//   stem_w, stem_b, stem_wm, w[0..9], pw[4], pw[8], bias[0..9], hcw[0..1], hcb[0..1], hfw[0..1], hfb[0..1], v2w, v2b
+int f16s_create(f16s_net** out, int board_size, int max_batch, int device) {
     if (!f16s_supported(board_size)) return -1;
     FS_HIP_OK(hipSetDevice(device));
     f16s_net* n = new f16s_net();
     n->S = board_size; n->max_batch = max_batch; n->device = device;
     const bool s11 = board_size == 11;
-    const int halves = s11 ? 1 : 2;
+    const int halves = s11 ? 1 : 2, npix = board_size * board_size;
     const size_t slab_bytes = s11 ? Lay<Geo<11>>::kSlabH : Lay<Geo<15>>::kSlabH;
-    FS_HIP_OK(hipDeviceGetAttribute(&n->ncu, hipDeviceAttributeMultiprocessorCount, device));
+    int rc = 0;
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) { fprintf(stderr, "[af_conv_f16s] %s failed: %s\n", what, hipGetErrorString(e)); rc = -2; }
+    };
+    hip(hipDeviceGetAttribute(&n->ncu, hipDeviceAttributeMultiprocessorCount, device), "hipDeviceGetAttribute");
     if (const char* e = getenv("AF_F16S_NCU")) {      // profiling only (tools/probe_power_bound.py): persistent workgroups of a launch = CUs it may occupy
         const int v = atoi(e);
         if (v >= 8 && v <= n->ncu) n->ncu = v / 8 * 8;
     }
-    int rc = 0;
-    auto get = [&](const std::string& k) -> const std::vector<float>& { return V.at(k); };
-    rc = dev_upload(n->allocs, &n->stem_w, get("bone/conv1/kernel").data(), 75 * 32 * 4);
-    if (!rc) rc = dev_upload(n->allocs, &n->stem_b, get("bone/conv1/bias").data(), 32 * 4);
-    if (!rc) {              // [k-step s][hi|lo][lane][8]: MFMA row m -> cout perm(m); k = 8*(lane>>5) + e of group g = 2s + (lane>>5) = cin*5 + ky, tap kx = e
-        const std::vector<float>& ks = get("bone/conv1/kernel");         // HWIO [5][5][3][32]
-        const float sc = pick_scale(ks, nullptr);
-        std::vector<_Float16> pk((size_t)8 * 2 * 64 * 8, (_Float16)0.0f);
-        for (int s_ = 0; s_ < 8; ++s_)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 5; ++e) {
-                    const int m = lane & 31, g = 2 * s_ + (lane >> 5);
-                    if (g >= 15) continue;
-                    const int co = 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3), cin = g / 5, ky = g % 5;
-                    const float v = ks[(size_t)((ky * 5 + e) * 3 + cin) * 32 + co] * sc;
-                    const _Float16 h = (_Float16)v;
-                    pk[(((size_t)s_ * 2 + 0) * 64 + lane) * 8 + e] = h;
-                    pk[(((size_t)s_ * 2 + 1) * 64 + lane) * 8 + e] = (_Float16)(v - (float)h);
-                }
-        rc = dev_upload(n->allocs, &n->stem_wm, pk.data(), pk.size() * 2);
-        n->stem_inv_scale = 1.0f / sc;
+    auto buf = [&](auto** p, size_t bytes, bool zero) { if (!rc) rc = dev_alloc(n, p, bytes, zero); };
+    auto wbuf = [&](auto** p, size_t bytes) { buf(p, bytes, false); if (!rc) n->wreg.push_back({*p, bytes}); };
+    wbuf(&n->stem_w, 75 * 32 * 4); wbuf(&n->stem_b, 32 * 4); wbuf(&n->stem_wm, kStemFrags * kFragBytes);
+    for (int l = 0; l < 10; ++l) wbuf(&n->w[l], layer_frags(kLayers[l]) * kFragBytes);
+    for (int l = 0; l < 10; ++l) if (kLayers[l].pj == 1) wbuf(&n->pw[l], proj_frags(kLayers[l], kLayers[l + 1].cout) * kFragBytes);
+    for (int l = 0; l < 10; ++l) wbuf(&n->bias[l], (size_t)kLayers[l].cout * 4);
+    for (int h = 0; h < 2; ++h) wbuf(&n->hcw[h], kHconvFrags * kFragBytes);
+    for (int h = 0; h < 2; ++h) wbuf(&n->hcb[h], 64);                                   // 16 floats: the head's couts, zero-padded
+    wbuf(&n->hfw[0], vfc_frags(npix) * kFragBytes); wbuf(&n->hfw[1], pfc_frags(npix) * kFragBytes);
+    wbuf(&n->hfb[0], 64 * 4); wbuf(&n->hfb[1], (size_t)npix * 4);
+    wbuf(&n->v2w, 64 * 4); wbuf(&n->v2b, 4);
+    // a separately produced projection: [pseudo-position][cout tile][4 pixel tiles][4][64] float4
+    for (int b = 0; b < 5; ++b)
+        if (kLayers[2 * b].pj == 1) buf(&n->pbuf[b], (size_t)max_batch * halves * (kLayers[2 * b + 1].cout / 32) * 4 * 4 * 64 * 16, false);
+    if (!s11) buf(&n->stash, (size_t)max_batch * 6 * 512, false);
+    buf(&n->df, kDfWords * sizeof(int), true);
+    buf(&n->pfx, 4 * 4 * 64 * 16, false);
+    auto act = [&](char** p, int ch) { buf(p, (size_t)max_batch * (ch / 32) * slab_bytes, true); };   // the zero units of S32 are never written again
+    act(&n->f0, 32);
+    for (int b = 0; b < 5; ++b) {
+        act(&n->g[b], kLayers[2 * b].cout);
+        if (b != 2 && b != 4) act(&n->o[b], kLayers[2 * b + 1].cout);
     }
-    for (int b = 0; b < 5 && !rc; ++b) {
-        const std::string s = kBlockNames[b];
-        const std::vector<float>&k1 = get(s + "_conv1/kernel"), &k2 = get(s + "_conv2/kernel"), &kr = get(s + "_res/kernel");
-        const LayerCfg &L1 = kLayers[2 * b], &L2 = kLayers[2 * b + 1];
-        const bool split_proj = L1.pj == 1;
-        const float s1 = pick_scale(k1, nullptr), s2 = pick_scale(k2, split_proj ? nullptr : &kr);
-        const std::vector<_Float16> p1 = pack_layer(L1, k1.data(), nullptr, s1), p2 = pack_layer(L2, k2.data(), kr.data(), s2);
-        rc = dev_upload(n->allocs, &n->w[2 * b], p1.data(), p1.size() * 2);
-        if (!rc && split_proj) {
-            const float sp = pick_scale(kr, nullptr);
-            const std::vector<_Float16> pp = pack_proj(L1, L2.cout, kr.data(), sp);
-            rc = dev_upload(n->allocs, &n->pw[2 * b], pp.data(), pp.size() * 2);
-            n->inv_scale_p[2 * b] = 1.0f / sp;
-            void* q = nullptr;
-            const size_t bytes = (size_t)max_batch * halves * (L2.cout / 32) * 4 * 4 * 64 * 16;      // [pseudo-position][cout tile][4 pixel tiles][4][64] float4
-            if (!rc) { FS_HIP_OK(hipMalloc(&q, bytes)); n->allocs.push_back(q); n->pbuf[b] = (float*)q; }
-        }
-
-        if (!rc) rc = dev_upload(n->allocs, &n->w[2 * b + 1], p2.data(), p2.size() * 2);
-        std::vector<float> bsum(get(s + "_conv2/bias"));
-        for (size_t i = 0; i < bsum.size(); ++i) bsum[i] += get(s + "_res/bias")[i];
-        if (!rc) rc = dev_upload(n->allocs, &n->bias[2 * b], get(s + "_conv1/bias").data(), L1.cout * 4);
-        if (!rc) rc = dev_upload(n->allocs, &n->bias[2 * b + 1], bsum.data(), L2.cout * 4);
-        n->inv_scale[2 * b] = 1.0f / s1; n->inv_scale[2 * b + 1] = 1.0f / s2;
-    }
-    auto act = [&](char** p, int ch) -> int {
-        void* q = nullptr;
-        const size_t bytes = (size_t)max_batch * (ch / 32) * slab_bytes;
-        FS_HIP_OK(hipMalloc(&q, bytes));
-        FS_HIP_OK(hipMemset(q, 0, bytes));           // the zero units of S32 are never written again
-        n->allocs.push_back(q);
-        *p = (char*)q;
-        return 0;
-    };
-    if (!rc && !s11) {
-        void* q = nullptr;
-        FS_HIP_OK(hipMalloc(&q, (size_t)max_batch * 6 * 512));
-        n->allocs.push_back(q);
-        n->stash = (char*)q;
-    }
-    if (!rc) {
-        void* q = nullptr;
-        FS_HIP_OK(hipMalloc(&q, kDfWords * sizeof(int)));
-        FS_HIP_OK(hipMemset(q, 0, kDfWords * sizeof(int)));
-        n->allocs.push_back(q);
-        n->df = (int*)q;
-        FS_HIP_OK(hipMalloc(&q, 4 * 4 * 64 * 16));
-        n->allocs.push_back(q);
-        n->pfx = (float*)q;
-    }
-    if (!rc) rc = act(&n->f0, 32);
-    for (int b = 0; b < 5 && !rc; ++b) {
-        rc = act(&n->g[b], kLayers[2 * b].cout);
-        if (!rc && b != 2 && b != 4) rc = act(&n->o[b], kLayers[2 * b + 1].cout);
-    }
-    if (!rc) {          // heads: value/conv [32][4], value/fc1 [4*S*S][64], value/fc2 [64][1]; policy/conv [32][16], policy/fc [16*S*S][S*S]
-        const int npix = board_size * board_size, hxp = 128 * halves, vsteps = (npix + 3) / 4, nlt = (npix + 31) / 32;
-        const char* cname[2] = {"value/conv", "policy/conv"};
-        const int nco[2] = {4, 16};
-        for (int h = 0; h < 2 && !rc; ++h) {
-            const std::vector<float>& wc = get(std::string(cname[h]) + "/kernel");
-            const float sc = pick_scale(wc, nullptr);
-            const int NC = nco[h];
-            const std::vector<_Float16> pk = pack_frags(2, [&](int st_, int lane, int e) -> float {
-                const int m = lane & 31, co = m < 16 ? 8 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3) : 99, ci = 16 * (lane >> 5) + 8 * st_ + e;
-                return co < NC ? wc[(size_t)ci * NC + co] * sc : 0.0f;
-            });
-            rc = dev_upload(n->allocs, &n->hcw[h], pk.data(), pk.size() * 2);
-            std::vector<float> bpad(16, 0.0f);
-            const std::vector<float>& bc = get(std::string(cname[h]) + "/bias");
-            for (int i = 0; i < NC; ++i) bpad[i] = bc[i];
-            if (!rc) rc = dev_upload(n->allocs, &n->hcb[h], bpad.data(), 64);
-            n->hc_inv[h] = 1.0f / sc;
-            void* q = nullptr;
-            const size_t bytes = (size_t)max_batch * hxp * (h == 0 ? 16 : 64);
-            if (!rc) { FS_HIP_OK(hipMalloc(&q, bytes)); FS_HIP_OK(hipMemset(q, 0, bytes)); n->allocs.push_back(q); n->hx[h] = (char*)q; }   // the pixel slots past S*S stay zero
-        }
-        if (!rc) {
-            const std::vector<float>& w1 = get("value/fc1/kernel");
-            const float sc = pick_scale(w1, nullptr);
-            const std::vector<_Float16> pk = pack_frags(vsteps * 2, [&](int f, int lane, int e) -> float {
-                const int s_ = f >> 1, mt = f & 1, px = 4 * s_ + 2 * (lane >> 5) + (e >> 2), ch = e & 3, j = 32 * mt + row_perm(lane & 31);
-                return px < npix ? w1[(size_t)(ch * npix + px) * 64 + j] * sc : 0.0f;
-            });
-            rc = dev_upload(n->allocs, &n->hfw[0], pk.data(), pk.size() * 2);
-            n->hf_inv[0] = 1.0f / sc;
-            if (!rc) rc = dev_upload(n->allocs, &n->hfb[0], get("value/fc1/bias").data(), 64 * 4);
-            if (!rc) rc = dev_upload(n->allocs, &n->v2w, get("value/fc2/kernel").data(), 64 * 4);
-            if (!rc) rc = dev_upload(n->allocs, &n->v2b, get("value/fc2/bias").data(), 4);
-        }
-        if (!rc) {
-            const std::vector<float>& wf = get("policy/fc/kernel");
-            const float sc = pick_scale(wf, nullptr);
-            const std::vector<_Float16> pk = pack_frags(npix * nlt, [&](int f, int lane, int e) -> float {
-                const int px = f / nlt, mt = f % nlt, c16 = 8 * (lane >> 5) + e, j = 32 * mt + row_perm(lane & 31);
-                return j < npix ? wf[(size_t)(c16 * npix + px) * npix + j] * sc : 0.0f;
-            });
-            rc = dev_upload(n->allocs, &n->hfw[1], pk.data(), pk.size() * 2);
-            n->hf_inv[1] = 1.0f / sc;
-            if (!rc) rc = dev_upload(n->allocs, &n->hfb[1], get("policy/fc/bias").data(), npix * 4);
-        }
-        if (!rc) FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_fc_f16s<Geo<11>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPfLds));
-        if (!rc) FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_fc_f16s<Geo<15>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPfLds));
-    }
+    for (int h = 0; h < 2; ++h) buf(&n->hx[h], (size_t)max_batch * 128 * halves * (h == 0 ? 16 : 64), true);   // the pixel slots past S*S stay zero
+    if (!rc) hip(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_fc_f16s<Geo<11>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPfLds), "hipFuncSetAttribute");
+    if (!rc) hip(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_fc_f16s<Geo<15>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPfLds), "hipFuncSetAttribute");
     if (rc) { f16s_destroy(n); return rc; }
-    fill_wreg(n);
     *out = n;
     return 0;
 }
@@ -2166,12 +1970,22 @@ void f16s_destroy(f16s_net* n) {
 }
 
 
-// ------------------------------------------- in-place weight update from device memory -------------------------------------------
-// af_net_update_device: the packers above (pack_layer, pack_proj, pack_frags, the stem) restated write-side, one thread per fragment
-// row (8 halves hi + 8 halves lo = two 16-byte stores), with the same index maps and the same arithmetic — v = w * scale (exact: a
-// power of two), hi = (_Float16)v (nearest even), lo = (_Float16)(v - (float)hi) — so that the bytes equal those of f16s_create.
-// The host packers stay the specification; tests/test_gpu_net_update.py compares the two byte for byte.
+// ------------------------------------------------ weight packing (device kernels) ------------------------------------------------
+// The only packers of this path: af_net_finalize (variables staged from the host) and af_net_update_device (variables already on
+// the device) both end in f16s_update_absmax + f16s_update_pack.  One thread per fragment row (8 halves hi + 8 halves lo = two
+// 16-byte stores); v = w * scale (exact: a power of two), hi = (_Float16)v (nearest even), lo = (_Float16)(v - (float)hi).
+// The specification of the bytes is tests/golden/packed_weight_digests.json — the digests of every packed buffer as the host
+// packers this code replaced produced them, which tests/test_gpu_net_update.py holds both entry points to — and, for the layouts
+// being right and not merely unchanged, the parity tests of the forward against the fp64 oracle and the reference fixtures.
 namespace {
+
+// scale of one group from its max|w| (NaN elements did not count towards it): an all-zero or non-finite maximum gives 1.0
+float pick_scale(float mx) {
+    if (!(mx > 0.0f) || !std::isfinite(mx)) return 1.0f;
+    int e;
+    std::frexp(mx, &e);                     // mx = f * 2^e, f in [0.5, 1)
+    return std::ldexp(1.0f, 13 - e);        // mx * scale in [4096, 8192): 8x below the fp16 maximum
+}
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
@@ -2180,7 +1994,7 @@ struct MaxTable { MaxGroup g[kF16sScaleGroups]; };
 constexpr int kMaxBlocks = 16;
 
 // max|w| of group blockIdx.y -> out[group] (zeroed before the launch; non-negative floats order as their bit patterns).  A NaN
-// element fails the comparison and does not count, +-inf does: what pick_scale's std::max(mx, std::fabs(v)) does.
+// element fails the comparison and does not count, +-inf does (pick_scale then answers 1.0).
 __global__ __launch_bounds__(256) void af_update_absmax(MaxTable T, float* __restrict__ out) {
     const MaxGroup g = T.g[blockIdx.y];
     float mx = 0.0f;
@@ -2200,15 +2014,21 @@ __global__ __launch_bounds__(256) void af_update_absmax(MaxTable T, float* __res
 }
 
 enum { FK_LAYER = 0, FK_STEM = 1, FK_HCONV = 2, FK_VFC = 3, FK_PFC = 4 };
-// one packed buffer: kind FK_LAYER = pack_layer (a produced projection is a layer of projection items only: cin = 0, pcin = the
-// producer's cin), w3 HWIO [9][cin][cout], w1 [pcin][cout]; the other kinds read w3 only; nc = couts of a head conv; npix = S*S
+// one packed buffer, [fragment][hi|lo][lane][8] halves; the other kinds than FK_LAYER read w3 only; nc = couts of a head conv; npix = S*S
+//   FK_LAYER  A fragments of one layer, fragment = [cout tile][ks][item]; item order = the kernel's consumption order (projection
+//             slabs first; per slab: 16-channel k-step c, then the 9 taps).  w3: HWIO [9][cin][cout]; w1: [pcin][cout] or null.
+//             A separately produced 1x1 projection is a layer of projection items only (cin = 0, pcin = the producer's cin,
+//             KS = the producer's): one item per (slab, 16-channel k-step), in the producer's order.
+//   FK_STEM   HWIO [5][5][3][32]: [k-step f][hi|lo][lane][8], k = 8*(lane>>5) + e of group g = 2f + (lane>>5) = cin*5 + ky, tap kx = e
+//   FK_HCONV  head 1x1 conv [32][nc]; FK_VFC value/fc1 [4*S*S][64]; FK_PFC policy/fc [16*S*S][S*S]
 struct FragDesc { uint4* dst; const float* w3; const float* w1; float scale; int kind, frags, cin, cout, pcin, KS, nc, npix; };
 constexpr int kMaxFragBufs = 17;
 struct FragTable { FragDesc d[kMaxFragBufs]; };
 
-__device__ __forceinline__ int dev_row_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }
+// MFMA row m of a 32-row tile -> the output it carries, such that a lane's 16 accumulator rows are 16 consecutive outputs
+__device__ __forceinline__ int row_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }
 
-// element e of lane `lane` of fragment f, scaled; the index maps of pack_layer / the stem loop / the pack_frags callers of f16s_create
+// element e of lane `lane` of fragment f, scaled: the index map of every fragment layout of this path
 __device__ __forceinline__ float frag_value(const FragDesc& D, int f, int lane, int e) {
 #pragma clang fp contract(off)
     const int m = lane & 31, kh = lane >> 5;
@@ -2221,25 +2041,25 @@ __device__ __forceinline__ float frag_value(const FragDesc& D, int f, int lane, 
             if (proj) { s = item / C16; c = item - s * C16; }
             else { const int it = item - NSP * C16; s = it / (9 * C16); c = (it / 9) % C16; tap = it % 9; }
             const int c16 = D.KS == 2 ? ks : c;
-            const int co = 32 * tile + dev_row_perm(m), ci = 32 * s + 16 * c16 + 8 * kh + e;
+            const int co = 32 * tile + row_perm(m), ci = 32 * s + 16 * c16 + 8 * kh + e;
             return (proj ? D.w1[(size_t)ci * D.cout + co] : D.w3[((size_t)tap * D.cin + ci) * D.cout + co]) * D.scale;
         }
-        case FK_STEM: {            // [k-step f][lane][8]: k group g = 2f + kh = cin*5 + ky, tap kx = e < 5
+        case FK_STEM: {            // k group g = 2f + kh = cin*5 + ky, tap kx = e < 5
             const int g = 2 * f + kh;
             if (e >= 5 || g >= 15) return 0.0f;
             const int cin = g / 5, ky = g - 5 * cin;
-            return D.w3[(size_t)((ky * 5 + e) * 3 + cin) * 32 + dev_row_perm(m)] * D.scale;
+            return D.w3[(size_t)((ky * 5 + e) * 3 + cin) * 32 + row_perm(m)] * D.scale;
         }
         case FK_HCONV: {
             const int co = m < 16 ? 8 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3) : 99, ci = 16 * kh + 8 * f + e;
             return co < D.nc ? D.w3[(size_t)ci * D.nc + co] * D.scale : 0.0f;
         }
         case FK_VFC: {
-            const int s_ = f >> 1, mt = f & 1, px = 4 * s_ + 2 * kh + (e >> 2), ch = e & 3, j = 32 * mt + dev_row_perm(m);
+            const int s_ = f >> 1, mt = f & 1, px = 4 * s_ + 2 * kh + (e >> 2), ch = e & 3, j = 32 * mt + row_perm(m);
             return px < D.npix ? D.w3[(size_t)(ch * D.npix + px) * 64 + j] * D.scale : 0.0f;
         }
         default: {                 // FK_PFC
-            const int nlt = (D.npix + 31) / 32, px = f / nlt, mt = f - px * nlt, c16 = 8 * kh + e, j = 32 * mt + dev_row_perm(m);
+            const int nlt = (D.npix + 31) / 32, px = f / nlt, mt = f - px * nlt, c16 = 8 * kh + e, j = 32 * mt + row_perm(m);
             return j < D.npix ? D.w3[(size_t)(c16 * D.npix + px) * D.npix + j] * D.scale : 0.0f;
         }
     }
@@ -2247,7 +2067,7 @@ __device__ __forceinline__ float frag_value(const FragDesc& D, int f, int lane, 
 
 constexpr int kFragBlocks = 64;
 // buffer blockIdx.y; a thread per fragment row (fragment f, lane): [f][hi|lo][lane] x 16 bytes
-__global__ __launch_bounds__(256) void af_update_pack_frags(FragTable T) {
+__global__ __launch_bounds__(256) void af_update_frags(FragTable T) {
 #pragma clang fp contract(off)
     const FragDesc& D = T.d[blockIdx.y];
     for (int row = blockIdx.x * 256 + threadIdx.x; row < D.frags * 64; row += kFragBlocks * 256) {
@@ -2316,7 +2136,7 @@ int f16s_update_absmax(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, floa
 int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const float* max_host) {
     const int npix = n->S * n->S;
     float sc[kF16sScaleGroups];
-    for (int g = 0; g < kF16sScaleGroups; ++g) sc[g] = pick_scale(std::vector<float>(1, max_host[g]), nullptr);
+    for (int g = 0; g < kF16sScaleGroups; ++g) sc[g] = pick_scale(max_host[g]);
     FragTable T = {};
     int nb = 0;
     auto frag = [&](uint4* dst, const float* w3, const float* w1, float scale, int kind, int frags, int cin, int cout, int pcin, int KS, int nc) {
@@ -2348,7 +2168,7 @@ int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const 
     copy(n->hfb[1], D.at("policy/fc/bias"), nullptr, npix, npix, 0);
     copy(n->v2w, D.at("value/fc2/kernel"), nullptr, 64, 64, 0);
     copy(n->v2b, D.at("value/fc2/bias"), nullptr, 1, 1, 0);
-    hipLaunchKernelGGL(af_update_pack_frags, dim3(kFragBlocks, nb), dim3(256), 0, st, T);
+    hipLaunchKernelGGL(af_update_frags, dim3(kFragBlocks, nb), dim3(256), 0, st, T);
     FS_HIP_OK(hipGetLastError());
     if (upd_launch_copies(st, C, ncp)) return -2;
     // forwards queued before this call took the old scales by value; later ones take these

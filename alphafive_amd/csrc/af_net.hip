@@ -50,7 +50,7 @@ __device__ __forceinline__ float elu1(float x) { return x > 0.0f ? x : __expf(x)
 //   * the block's 1x1 projection is a 3x3 kernel with only the centre tap set; in the Winograd
 //     domain only (xi,nu) in {1,2}^2 are non-zero, so it is 4 extra k-steps per cin pair into
 //     M[1][1], M[1][2], M[2][1], M[2][2] and needs only the 2x2 centre of the patch.
-//   * U = G g G^T is computed once on the host (fp64, rounded to fp32) and packed k-pair-major
+//   * U = G g G^T is computed once per weight set (af_update_wino: fp64, rounded to fp32) and packed k-pair-major
 //     [cin/2][2][cout][16] (a lane's 16 values = 4 dwordx4 loads); the 4 waves of a workgroup take 4 tile blocks of the SAME cout tile so
 //     the weight stream is shared in L1.
 // Plane layout: tiles need rows/cols 2t-1 .. 2t+2, so planes are padded to (2*ceil(S/2)+2)^2.
@@ -610,7 +610,7 @@ struct af_net {
     // activations [max_batch][C][PP]
     float *f0, *g[5], *o[5];
     f16s_net* f16s = nullptr;     // 11x11 boards: the fp16 split-operand convolution path (af_conv_f16s.hip)
-    // af_net_update_device: max|w| per scale group of the split-operand path, device and pinned host (created once, by the first finalize)
+    // weight packing: max|w| per scale group of the split-operand path, device and pinned host (created once, by the first finalize)
     float *upd_max_dev = nullptr, *upd_max_host = nullptr;
     std::vector<std::pair<const void*, size_t>> wreg;   // weight-derived buffers of this path, in af_net_debug_weights' order
 };
@@ -626,47 +626,15 @@ static int net_alloc(af_net* n, T** p, size_t count, bool zero) {
     *p = (T*)q;
     return AF_NET_OK;
 }
-static int net_upload(af_net* n, float** p, const std::vector<float>& h) {
-    int rc = net_alloc(n, p, h.size(), false);
-    if (rc) return rc;
-    NET_HIP_OK(hipMemcpy(*p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    return AF_NET_OK;
-}
 
-// Winograd weights U = G g G^T per (cin, cout), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], packed
-// [cin/2][2][cout][npos] (one lane's npos values contiguous).  taps == 9: all 16 (xi,nu); taps == 1: the centre-tap kernel of a 1x1
-// projection, whose only non-zero positions are (1,1),(1,2),(2,1),(2,2).
-static std::vector<float> pack_wino(const std::vector<float>& w, int taps, int cin, int cout) {
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    static const int kCentre[4] = {5, 6, 9, 10};
-    const int npos = taps == 9 ? 16 : 4;
-    std::vector<float> out((size_t)cin * npos * cout, 0.0f);
-    for (int c = 0; c < cin; ++c)
-        for (int co = 0; co < cout; ++co) {
-            double g[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-            if (taps == 9) {
-                for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = w[((size_t)t * cin + c) * cout + co];
-            } else {
-                g[1][1] = w[(size_t)c * cout + co];
-            }
-            for (int p = 0; p < npos; ++p) {
-                const int x = taps == 9 ? p : kCentre[p];
-                const int xi = x / 4, nu = x % 4;
-                double u = 0.0;
-                for (int i = 0; i < 3; ++i)
-                    for (int j = 0; j < 3; ++j) u += G[xi][i] * g[i][j] * G[nu][j];
-                out[((((size_t)(c / 2) * 2) + (c & 1)) * cout + co) * npos + p] = (float)u;
-            }
-        }
-    return out;
-}
-// pack_wino restated write-side for af_net_update_device: a thread per (cin, cout) pair reads the pair's taps from DEVICE memory and
-// writes its npos values of U = G g G^T: fp64, the same i, j summation order, no contraction, then rounded to fp32 — the bytes of
-// pack_wino (tests/test_gpu_net_update.py compares them).
+// Winograd weights U = G g G^T per (cin, cout), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], packed [cin/2][2][cout][npos] (one
+// lane's npos values contiguous).  taps == 9: all 16 (xi,nu); taps == 1: the centre-tap kernel of a 1x1 projection, whose only
+// non-zero positions are (1,1),(1,2),(2,1),(2,2).  A thread per (cin, cout) pair reads the pair's taps (HWIO, device memory) and
+// writes its npos values: fp64, summed over i then j, no contraction, then rounded to fp32.
 struct WinoPackDesc { const float* w; float* out; int taps, cin, cout; };
 constexpr int kWinoBufs = 15, kWinoPackBlocks = 64;
 struct WinoPackTable { WinoPackDesc d[kWinoBufs]; };
-__global__ __launch_bounds__(256) void af_update_pack_wino(WinoPackTable T) {
+__global__ __launch_bounds__(256) void af_update_wino(WinoPackTable T) {
 #pragma clang fp contract(off)
     const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     const WinoPackDesc& D = T.d[blockIdx.y];
@@ -700,10 +668,43 @@ __global__ __launch_bounds__(256) void af_update_pack_wino(WinoPackTable T) {
     }
 }
 
-static std::vector<float> pad_bias(const std::vector<float>& a, const std::vector<float>* b, int cout) {
-    std::vector<float> out(pad32(cout), 0.0f);
-    for (int i = 0; i < cout; ++i) out[i] = a[i] + (b ? (*b)[i] : 0.0f);
-    return out;
+// Packs every weight-derived buffer of the handle, in place, from the 42 fp32 TF-layout tensors D names in device memory: the one
+// packer behind af_net_finalize and af_net_update_device.  Asynchronous on st but for ONE wait: the scales of the split-operand
+// path need max|w| per group, reduced on the device and brought to the host as 80 bytes.
+static int pack_from_device(af_net* n, hipStream_t st, const f16s_dev_vars& D) {
+    if (n->f16s) {
+        if (f16s_update_absmax(n->f16s, st, D, n->upd_max_dev)) return AF_NET_ERR_HIP;
+        NET_HIP_OK(hipMemcpyAsync(n->upd_max_host, n->upd_max_dev, kF16sScaleGroups * sizeof(float), hipMemcpyDeviceToHost, st));
+        NET_HIP_OK(hipStreamSynchronize(st));
+        if (f16s_update_pack(n->f16s, st, D, n->upd_max_host)) return AF_NET_ERR_HIP;
+    }
+    WinoPackTable W = {};
+    UpdCopy C[22];
+    int ncp = 0;
+    auto copy = [&](float* dst, const char* a, const float* b, size_t n_dst, int sum) {
+        C[ncp++] = UpdCopy{dst, D.at(a), b, (int)n_dst, (int)n->expect.at(a), sum};
+    };
+    copy(n->stem_w, "bone/conv1/kernel", nullptr, 75 * 32, 0); copy(n->stem_b, "bone/conv1/bias", nullptr, 32, 0);
+    for (int i = 0; i < 5; ++i) {
+        const Block& b = kBlocks[i];
+        const std::string s = b.name;
+        // biases padded with zeros to a multiple of 32 couts; conv1's is bias + 0.0f, conv2's the sum with the projection's
+        copy(n->conv1_b[i], (s + "_conv1/bias").c_str(), nullptr, pad32(b.cout), 1);
+        copy(n->sum_b[i], (s + "_conv2/bias").c_str(), D.at(s + "_res/bias"), pad32(b.cout), 1);
+        W.d[3 * i] = WinoPackDesc{D.at(s + "_conv1/kernel"), n->wino1_u[i], 9, b.cin, b.cout};
+        W.d[3 * i + 1] = WinoPackDesc{D.at(s + "_conv2/kernel"), n->wino2_u[i], 9, b.cout, b.cout};
+        W.d[3 * i + 2] = WinoPackDesc{D.at(s + "_res/kernel"), n->winor_u[i], 1, b.cin, b.cout};
+    }
+    const size_t HW = n->HW;
+    copy(n->vc_w, "value/conv/kernel", nullptr, 32 * 4, 0); copy(n->vc_b, "value/conv/bias", nullptr, 4, 0);
+    copy(n->v1_w, "value/fc1/kernel", nullptr, 4 * HW * 64, 0); copy(n->v1_b, "value/fc1/bias", nullptr, 64, 0);
+    copy(n->v2_w, "value/fc2/kernel", nullptr, 64, 0); copy(n->v2_b, "value/fc2/bias", nullptr, 1, 0);
+    copy(n->pc_w, "policy/conv/kernel", nullptr, 32 * 16, 0); copy(n->pc_b, "policy/conv/bias", nullptr, 16, 0);
+    copy(n->pf_w, "policy/fc/kernel", nullptr, 16 * HW * HW, 0); copy(n->pf_b, "policy/fc/bias", nullptr, HW, 0);
+    hipLaunchKernelGGL(af_update_wino, dim3(kWinoPackBlocks, kWinoBufs), dim3(256), 0, st, W);
+    NET_HIP_OK(hipGetLastError());
+    if (upd_launch_copies(st, C, ncp)) return AF_NET_ERR_HIP;
+    return AF_NET_OK;
 }
 
 extern "C" {
@@ -777,25 +778,24 @@ int af_net_finalize(af_net* n) {
     n->allocs.clear();
     f16s_destroy(n->f16s);
     n->f16s = nullptr;
-    if (f16s_supported(n->S) && f16s_create(&n->f16s, n->S, n->max_batch, n->device, n->vars) != 0) return AF_NET_ERR_HIP;
-    auto& V = n->vars;
+    if (f16s_supported(n->S) && f16s_create(&n->f16s, n->S, n->max_batch, n->device) != 0) return AF_NET_ERR_HIP;
     int rc = AF_NET_OK;
-#define UP(dst, vec) if (!rc) rc = net_upload(n, &n->dst, (vec))
-    UP(stem_w, V["bone/conv1/kernel"]); UP(stem_b, V["bone/conv1/bias"]);
-    for (int i = 0; i < 5; ++i) {
-        const Block& b = kBlocks[i];
-        const std::string s = b.name;
-        UP(conv1_b[i], pad_bias(V[s + "_conv1/bias"], nullptr, b.cout));
-        UP(sum_b[i], pad_bias(V[s + "_conv2/bias"], &V[s + "_res/bias"], b.cout));
-        UP(wino1_u[i], pack_wino(V[s + "_conv1/kernel"], 9, b.cin, b.cout));
-        UP(wino2_u[i], pack_wino(V[s + "_conv2/kernel"], 9, b.cout, b.cout));
-        UP(winor_u[i], pack_wino(V[s + "_res/kernel"], 1, b.cin, b.cout));
-    }
-    UP(vc_w, V["value/conv/kernel"]); UP(vc_b, V["value/conv/bias"]); UP(v1_w, V["value/fc1/kernel"]);
-    UP(v1_b, V["value/fc1/bias"]); UP(v2_w, V["value/fc2/kernel"]); UP(v2_b, V["value/fc2/bias"]);
-    UP(pc_w, V["policy/conv/kernel"]); UP(pc_b, V["policy/conv/bias"]); UP(pf_w, V["policy/fc/kernel"]);
-    UP(pf_b, V["policy/fc/bias"]);
-#undef UP
+    // the fp32 path's weight-derived buffers, registered in af_net_debug_weights' order as they are allocated (the split-operand
+    // path's follow: f16s_weight_buffer), so what is allocated and what af_net_debug_weights reports cannot differ; pack_from_device fills them
+    n->wreg.clear();
+    auto wbuf = [&](float** p, size_t count) {
+        if (!rc) rc = net_alloc(n, p, count, false);
+        if (!rc) n->wreg.push_back({*p, count * sizeof(float)});
+    };
+    const size_t HW = n->HW;
+    wbuf(&n->stem_w, 75 * 32); wbuf(&n->stem_b, 32);
+    for (int i = 0; i < 5; ++i) wbuf(&n->conv1_b[i], pad32(kBlocks[i].cout));
+    for (int i = 0; i < 5; ++i) wbuf(&n->sum_b[i], pad32(kBlocks[i].cout));
+    for (int i = 0; i < 5; ++i) wbuf(&n->wino1_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 16);
+    for (int i = 0; i < 5; ++i) wbuf(&n->wino2_u[i], (size_t)kBlocks[i].cout * kBlocks[i].cout * 16);
+    for (int i = 0; i < 5; ++i) wbuf(&n->winor_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 4);
+    wbuf(&n->vc_w, 32 * 4); wbuf(&n->vc_b, 4); wbuf(&n->v1_w, 4 * HW * 64); wbuf(&n->v1_b, 64); wbuf(&n->v2_w, 64); wbuf(&n->v2_b, 1);
+    wbuf(&n->pc_w, 32 * 16); wbuf(&n->pc_b, 16); wbuf(&n->pf_w, 16 * HW * HW); wbuf(&n->pf_b, HW);
     const size_t plane = (size_t)n->max_batch * n->PP;
     if (!rc) rc = net_alloc(n, &n->f0, plane * 32, true);
     for (int i = 0; i < 5 && !rc; ++i) {
@@ -810,27 +810,25 @@ int af_net_finalize(af_net* n) {
         NET_HIP_OK(hipEventCreateWithFlags(&n->ev_trunk, hipEventDisableTiming));
         NET_HIP_OK(hipEventCreateWithFlags(&n->ev_value, hipEventDisableTiming));
     }
-    if (!n->upd_max_dev) {       // af_net_update_device allocates nothing: its two small buffers are made here, once per handle
+    if (!n->upd_max_dev) {       // af_net_update_device allocates nothing: the packer's two small buffers are made here, once per handle
         NET_HIP_OK(hipMalloc((void**)&n->upd_max_dev, kF16sScaleGroups * sizeof(float)));
         NET_HIP_OK(hipHostMalloc((void**)&n->upd_max_host, kF16sScaleGroups * sizeof(float), hipHostMallocDefault));
     }
-    {   // af_net_debug_weights' order on this path (the split-operand path's buffers follow: f16s_weight_buffer)
-        const size_t HW = n->HW;
-        auto& R = n->wreg;
-        R.clear();
-        R.push_back({n->stem_w, 75 * 32 * 4}); R.push_back({n->stem_b, 32 * 4});
-        for (int i = 0; i < 5; ++i) R.push_back({n->conv1_b[i], (size_t)pad32(kBlocks[i].cout) * 4});
-        for (int i = 0; i < 5; ++i) R.push_back({n->sum_b[i], (size_t)pad32(kBlocks[i].cout) * 4});
-        for (int i = 0; i < 5; ++i) R.push_back({n->wino1_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 16 * 4});
-        for (int i = 0; i < 5; ++i) R.push_back({n->wino2_u[i], (size_t)kBlocks[i].cout * kBlocks[i].cout * 16 * 4});
-        for (int i = 0; i < 5; ++i) R.push_back({n->winor_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 4 * 4});
-        R.push_back({n->vc_w, 32 * 4 * 4}); R.push_back({n->vc_b, 4 * 4}); R.push_back({n->v1_w, 4 * HW * 64 * 4});
-        R.push_back({n->v1_b, 64 * 4}); R.push_back({n->v2_w, 64 * 4}); R.push_back({n->v2_b, 4});
-        R.push_back({n->pc_w, 32 * 16 * 4}); R.push_back({n->pc_b, 16 * 4}); R.push_back({n->pf_w, 16 * HW * HW * 4});
-        R.push_back({n->pf_b, HW * 4});
-    }
-    n->ready = true;
-    return AF_NET_OK;
+    // stage the variables on the device in n->vars' order — one host image, one allocation, one copy — and pack from there
+    std::vector<float> image;
+    for (auto& kv : n->vars) image.insert(image.end(), kv.second.begin(), kv.second.end());
+    float* stage = nullptr;
+    NET_HIP_OK(hipMalloc((void**)&stage, image.size() * sizeof(float)));
+    f16s_dev_vars D;
+    size_t off = 0;
+    for (auto& kv : n->vars) { D[kv.first] = stage + off; off += kv.second.size(); }
+    rc = hipMemcpy(stage, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? AF_NET_OK : AF_NET_ERR_HIP;
+    if (!rc) rc = pack_from_device(n, nullptr, D);
+    // every pack kernel has finished before this returns: a forward on any stream finds the weights, and the staging can go
+    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = AF_NET_ERR_HIP;
+    (void)hipFree(stage);
+    n->ready = rc == AF_NET_OK;
+    return rc;
 }
 
 int af_net_update_device(af_net* n, void* stream, const char* const* tf_names, const float* const* dev_ptrs, const int64_t* counts,
@@ -851,38 +849,8 @@ int af_net_update_device(af_net* n, void* stream, const char* const* tf_names, c
     NET_HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return AF_NET_ERR_STATE;                // this call waits for the stream once: not capturable
     NET_HIP_OK(hipSetDevice(n->device));
-    if (n->f16s) {
-        // the scales of the split-operand path need max|w| per group: reduced on the device, 80 bytes to the host, ONE wait
-        if (f16s_update_absmax(n->f16s, st, D, n->upd_max_dev)) return AF_NET_ERR_HIP;
-        NET_HIP_OK(hipMemcpyAsync(n->upd_max_host, n->upd_max_dev, kF16sScaleGroups * sizeof(float), hipMemcpyDeviceToHost, st));
-        NET_HIP_OK(hipStreamSynchronize(st));
-        if (f16s_update_pack(n->f16s, st, D, n->upd_max_host)) return AF_NET_ERR_HIP;
-    }
-    WinoPackTable W = {};
-    UpdCopy C[22];
-    int ncp = 0;
-    auto copy = [&](float* dst, const char* a, const float* b, size_t n_dst, int sum) {
-        C[ncp++] = UpdCopy{dst, D.at(a), b, (int)n_dst, (int)n->expect.at(a), sum};
-    };
-    copy(n->stem_w, "bone/conv1/kernel", nullptr, 75 * 32, 0); copy(n->stem_b, "bone/conv1/bias", nullptr, 32, 0);
-    for (int i = 0; i < 5; ++i) {
-        const Block& b = kBlocks[i];
-        const std::string s = b.name;
-        copy(n->conv1_b[i], (s + "_conv1/bias").c_str(), nullptr, pad32(b.cout), 1);          // pad_bias: a + 0.0f
-        copy(n->sum_b[i], (s + "_conv2/bias").c_str(), D.at(s + "_res/bias"), pad32(b.cout), 1);
-        W.d[3 * i] = WinoPackDesc{D.at(s + "_conv1/kernel"), n->wino1_u[i], 9, b.cin, b.cout};
-        W.d[3 * i + 1] = WinoPackDesc{D.at(s + "_conv2/kernel"), n->wino2_u[i], 9, b.cout, b.cout};
-        W.d[3 * i + 2] = WinoPackDesc{D.at(s + "_res/kernel"), n->winor_u[i], 1, b.cin, b.cout};
-    }
-    const size_t HW = n->HW;
-    copy(n->vc_w, "value/conv/kernel", nullptr, 32 * 4, 0); copy(n->vc_b, "value/conv/bias", nullptr, 4, 0);
-    copy(n->v1_w, "value/fc1/kernel", nullptr, 4 * HW * 64, 0); copy(n->v1_b, "value/fc1/bias", nullptr, 64, 0);
-    copy(n->v2_w, "value/fc2/kernel", nullptr, 64, 0); copy(n->v2_b, "value/fc2/bias", nullptr, 1, 0);
-    copy(n->pc_w, "policy/conv/kernel", nullptr, 32 * 16, 0); copy(n->pc_b, "policy/conv/bias", nullptr, 16, 0);
-    copy(n->pf_w, "policy/fc/kernel", nullptr, 16 * HW * HW, 0); copy(n->pf_b, "policy/fc/bias", nullptr, HW, 0);
-    hipLaunchKernelGGL(af_update_pack_wino, dim3(kWinoPackBlocks, kWinoBufs), dim3(256), 0, st, W);
-    NET_HIP_OK(hipGetLastError());
-    if (upd_launch_copies(st, C, ncp)) return AF_NET_ERR_HIP;
+    const int rc = pack_from_device(n, st, D);
+    if (rc) return rc;
     n->vars.clear();             // the host copy is stale: af_net_finalize needs all 42 variables set again
     n->ready = true;
     return AF_NET_OK;

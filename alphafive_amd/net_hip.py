@@ -66,7 +66,8 @@ class HipNet(object):
         self.value = torch.empty((max_batch,), dtype=torch.float32, device=self.device)
 
     def load(self, variables):
-        """(Re)load a weight set: af_net_set_variable for every tensor, then af_net_finalize repacks and uploads."""
+        """(Re)load a weight set from host arrays: af_net_set_variable for every tensor, then af_net_finalize re-creates the handle's
+        buffers, uploads the tensors as they are and packs them on the device (the kernels of load_device); done when it returns."""
         torch.cuda.synchronize(self.device)             # no forward may still be reading the old packed weights
         for name, arr in variables.items():
             a = np.ascontiguousarray(arr, np.float32)

@@ -34,13 +34,15 @@ void af_net_destroy(af_net* n);
 
 /* Provide one variable (host pointer, fp32, TF layout) — e.g. "bone/block1_conv1/kernel". */
 int af_net_set_variable(af_net* n, const char* tf_name, const float* host_data, int64_t count);
-/* Repack (k-pair-major streams for the MFMA kernels) and upload; call after all 42 variables are set. */
+/* Call after all 42 variables are set: (re-)creates the handle's device buffers, uploads the variables to a temporary device buffer
+ * and packs them there with the kernels of af_net_update_device (k-pair-major streams and split fp16 fragments for the MFMA
+ * kernels).  The packing has finished and the temporary buffer is gone when it returns. */
 int af_net_finalize(af_net* n);
 
 /* Weight hand-over without the host: all 42 variables at once, from DEVICE memory (fp32, TF layout, same names / counts as
  * af_net_set_variable), re-packed by kernels IN PLACE into the buffers the handle already owns — nothing is freed, nothing is
  * allocated, no weight is copied to the host.  Every weight-derived buffer of BOTH conv paths is rewritten (af_net_tune(0, .) may
- * switch paths at any time), to the bytes af_net_set_variable + af_net_finalize make of the same values.
+ * switch paths at any time), to the bytes af_net_set_variable + af_net_finalize make of the same values (the same kernels pack).
  *   - the handle must have been finalized once (AF_NET_ERR_STATE otherwise);
  *   - all or nothing: names, counts and "each of the 42 exactly once" are checked before anything is launched — an unknown name or a
  *     wrong count returns AF_NET_ERR_NAME; a null handle / array / entry, nvars != 42 or a name given twice AF_NET_ERR_ARG (null

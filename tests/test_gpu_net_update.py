@@ -1,7 +1,13 @@
 """af_net_update_device: weights re-packed on the device, in place, must be the bytes af_net_set_variable + af_net_finalize make of
 the same values — every weight-derived buffer of both conv paths and every scale — and therefore the same forward, bit for bit;
 the update is ordered on its stream, all or nothing, refused under capture, and is what train_loop(weights_on_device=True) hands
-the evaluator through ResNet.set_variables_device / net_hip.make_eval."""
+the evaluator through ResNet.set_variables_device / net_hip.make_eval.
+
+Both entry points end in the same device packers, so their agreement alone would say little: what pins the bytes is
+tests/golden/packed_weight_digests.json, the digests of every buffer as the host packers those kernels replaced produced them
+(tests/golden/make_packed_weight_digests.py)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -12,6 +18,22 @@ from conftest import GOLDEN
 pytestmark = pytest.mark.gpu
 W = os.path.join(GOLDEN, "alphaFive-6960.weights.npz")
 N_FP32_BUFFERS, N_SPLIT_BUFFERS, N_SCALES = 37, 35, 25          # include/af_net.h: af_net_debug_weights / af_net_debug_scales
+DIGESTS = os.path.join(GOLDEN, "packed_weight_digests.json")
+_recorded = {}
+
+
+def _assert_recorded_state(H, key, what):
+    """every buffer of H and every scale is what the host packers made of weight set `key` (packed_weight_digests.json)"""
+    if not _recorded:
+        with open(DIGESTS) as f:
+            _recorded.update(json.load(f))
+    rec = _recorded[key]
+    got = [hashlib.sha256(b.tobytes()).hexdigest() for b in H.debug_weights()]
+    assert len(got) == len(rec["buffers"]), (what, len(got), len(rec["buffers"]))
+    for i, (g, r) in enumerate(zip(got, rec["buffers"])):
+        assert g == r, "%s: buffer %d is not the recorded one of %s" % (what, i, key)
+    scales = [int(u) for u in H.debug_scales().view(np.uint32)]
+    assert scales == rec["scales"], (what, key, scales, rec["scales"])
 
 
 def _positions(S, B, seed=0):
@@ -101,8 +123,11 @@ def test_device_update_packs_the_bytes_of_the_host_path(case, variant):
     S = case[0]
     V = _variant(_weights(case), variant)
     A, B, _ = _pair(S, V, 8, check_changed=True)
+    key = "%dx%d-%s-%s" % (S, S, case[1], variant)
     try:
         scales = _assert_same_state(A, B, S)
+        _assert_recorded_state(A, key, "A (af_net_finalize)")
+        _assert_recorded_state(B, key, "B (af_net_update_device)")
         if variant == "zero" and scales.size:
             assert scales[1 + 5] == 1.0         # layer 5 = value/block3 conv2, its projection produced separately: an all-zero group
     finally:
@@ -174,6 +199,42 @@ def test_update_is_ordered_on_its_stream_between_two_forwards():
     finally:
         for h in (H, H0, H1):
             h.close()
+
+
+def test_host_load_after_a_device_update_restores_the_first_weights_for_any_stream():
+    """load(V0) -> load_device(V1) -> load(V0) on one handle: the recorded bytes of V0 again and V0's forward bit for bit — also for
+    a forward queued on a fresh non-default stream right behind load(), with no wait of the test's own: af_net_finalize packs
+    with kernels out of a staging buffer it has freed by then, and has to have finished them before it returns."""
+    import torch
+    from alphafive_amd import net_hip
+    S, nb = 11, 8
+    V0, V1 = _weights((11, "ckpt")), _random_weights(11, 5)
+    H0 = net_hip.HipNet(V0, S, nb, "cuda")          # only ever sees V0
+    H = net_hip.HipNet(V0, S, nb, "cuda")
+    try:
+        x = torch.from_numpy(_positions(S, nb, seed=9)).cuda()
+        p0, v0 = _forward(H0, x)
+        pa, va = _forward(H, x)
+        assert np.array_equal(p0.view(np.uint32), pa.view(np.uint32)) and np.array_equal(v0.view(np.uint32), va.view(np.uint32))
+        H.load_device(_dev(V1))
+        p1, v1 = _forward(H, x)
+        assert not np.array_equal(p0, p1) and not np.array_equal(v0, v1)
+        out = (torch.zeros(nb, S * S, device="cuda"), torch.zeros(nb, device="cuda"))
+        s = torch.cuda.Stream()
+        torch.cuda.synchronize()                    # (x, out and the stream exist; nothing of ours waits from here to the forward)
+        H.load(V0)
+        with torch.cuda.stream(s):
+            H.bind_outputs(*out)
+            H(x)
+        s.synchronize()
+        p2, v2 = out[0].cpu().numpy(), out[1].cpu().numpy()
+        assert np.array_equal(p0.view(np.uint32), p2.view(np.uint32)) and np.array_equal(v0.view(np.uint32), v2.view(np.uint32))
+        _assert_recorded_state(H, "11x11-ckpt-plain", "load, load_device, load")
+        p3, v3 = _forward(H, x)                     # ... and on the default stream
+        assert np.array_equal(p0.view(np.uint32), p3.view(np.uint32)) and np.array_equal(v0.view(np.uint32), v3.view(np.uint32))
+    finally:
+        H.close()
+        H0.close()
 
 
 def _synthetic_batch(rng, S, n=64):
