@@ -16,21 +16,43 @@ int f16s_supported(int board_size);
 // allocates every device buffer of the handle; the weight-derived ones hold nothing until the first f16s_update_pack
 int f16s_create(f16s_net** out, int board_size, int max_batch, int device);
 void f16s_destroy(f16s_net* n);
-// stem + bone/block1 + bone/block2 on stream st
-int f16s_trunk(f16s_net* n, hipStream_t st, const float* planes_dev, int batch);
-// value/block3 -> o3, policy/block4+5 -> o5: fp32 planes [batch][32][PP], pixel (y,x) at (y+1)*WP + x+1 (the head kernels' input)
-// value / policy != nullptr: the branch's last conv also applies the head's 1x1 convolution and the head's dense layers run on the
-// same split-operand MFMA (af_value_fc_f16s / af_policy_fc_f16s) -> value [batch] / policy [batch][121]; o3 / o5 are then not written
-int f16s_value_branch(f16s_net* n, hipStream_t st, int batch, float* o3_dev, int WP, int PP, float* value);
-int f16s_policy_branch(f16s_net* n, hipStream_t st, int batch, float* o5_dev, int WP, int PP, float* policy);
-// batches <= 8 on 11x11, heads fused: both branches on one stream ({policy conv1 || value block} in one launch): no side stream
-int f16s_small_branches_ok(const f16s_net* n, int batch);          // (abl bit 9 = the two-stream form, for A/B)
-int f16s_small_branches(f16s_net* n, hipStream_t st, int batch, float* value, float* policy);
-// batches <= 8 on 11x11 (r6): the whole forward up to the policy head's input as ONE launch of dataflow roles + the policy dense layer
-int f16s_small_forward_ok(const f16s_net* n, int batch);           // (abl bit 11 = the multi-launch form, for A/B)
-int f16s_small_forward(f16s_net* n, hipStream_t st, const float* planes_dev, int batch, float* value, float* policy);
-int f16s_small_forward_error(f16s_net* n);                         // 1 if a role ever gave up waiting (synchronises)
-void f16s_set_ablation(f16s_net* n, int bits);
+// ---- the launch plan: which launches a forward of `batch` positions is made of ----
+// af_net_tune key 7 (include/af_net.h describes the bits by these names).  The profiling bits reach the kernels (F16sArgs::abl) and
+// make the results wrong by design; every other bit selects the launch structure the default replaced.
+enum F16sBits : int {
+    kF16sProfilingBits = 1 | 2 | 4 | 8 | 4096,   // no slab loads after the first position / no stores / loads from a hot address / stores, loads modulo 128 positions
+    kF16sValuStem = 16,              // the VALU stem (af_stem_f16s) instead of the MFMA one
+    kF16sOneWgPerCu = 32,            // 11x11, the 32-channel-input layers: one workgroup per CU instead of two
+    kF16sTwoHalves15 = 64,           // 15x15: the two-halves launch instead of the 4-tile / 3-tile classes + corner kernel
+    kF16sWgPerPosition = 128,        // batches <= 8: one workgroup per position instead of the pixel-tile split
+    kF16sTwoLaunchBlocks = 256,      // 11x11: two launches per 32-wide block instead of af_block_f16s
+    kF16sBranchLaunchesSmall = 512,  // 11x11, batches <= 8: the two-branch launch order instead of the value branch as a workgroup class
+    kF16sBranchLaunchesBig = 1024,   // ... and above 8
+    kF16sLaunchSequence = 2048,      // 11x11, batches <= 8: nine dependent launches instead of the single launch of dataflow roles
+};
+enum F16sForm {
+    kF16sRoles,      // batches <= 8 on 11x11: the whole forward up to the policy head's input as ONE launch of dataflow roles + the policy dense layer
+    kF16sPaired,     // 11x11: trunk, then both branches on one stream ({policy conv1 || value block} in one launch): no side stream
+    kF16sBranches,   // trunk, then f16s_value_branch and f16s_policy_branch (the caller picks their streams)
+};
+// every choice between launch variants, made once per forward by f16s_plan and nowhere else
+struct F16sPlan {
+    int batch, bits;
+    bool heads;             // the path computes the heads itself (af_net_tune key 9)
+    F16sForm form;          // kF16sRoles and kF16sPaired need `heads`
+    bool valu_stem, two_wg_per_cu, half_classes, tile_split, fused_blocks;
+};
+F16sPlan f16s_plan(const f16s_net* n, int batch, int bits, bool heads);
+// forms kF16sRoles and kF16sPaired: the whole forward on stream st -> value [batch], policy [batch][121]
+int f16s_forward(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes_dev, float* value, float* policy);
+// form kF16sBranches, in three parts.  Stem + bone/block1 + bone/block2 on stream st:
+int f16s_trunk(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes_dev);
+// value/block3, policy/block4+5.  p.heads: the branch's last conv also applies the head's 1x1 convolution and the head's dense layer
+// runs on the same split-operand MFMA (af_value_fc_f16s / af_policy_fc_f16s) -> value [batch] / policy [batch][S*S].  Otherwise
+// -> o3 / o5: fp32 planes [batch][32][PP], pixel (y,x) at (y+1)*WP + x+1 (the fp32 head kernels' input)
+int f16s_value_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o3_dev, int WP, int PP, float* value);
+int f16s_policy_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o5_dev, int WP, int PP, float* policy);
+int f16s_small_forward_error(f16s_net* n);                         // 1 if a role of kF16sRoles ever gave up waiting (synchronises)
 int f16s_read_activation(f16s_net* n, int which, int batch, float* host);
 
 // ---- weight packing, from device memory and in place: the one packer of this path (af_net_finalize over the variables it staged,

@@ -1747,49 +1747,61 @@ extern "C" int af_pfc_debug_wall(unsigned long long* host) {
 #endif
 
 // ------------------------------------------------------------------ host ------------------------------------------------------------------
-struct LayerCfg { int cin, cout, pcin, CT, KS, PS, gy, pj; };
-// block b: conv1 = layer 2b, conv2 (+ projection) = layer 2b+1.  pcin: channels of the projection input folded into this
+struct LayerCfg { int cin, cout, pcin, CT, KS, PS, gy, pj; bool xacc; };
+// The ten layers, stated once: the packers size and lay out fragments from this table and launch_one instantiates the kernels from it.
+// Block b: conv1 = layer 2b, conv2 (+ projection) = layer 2b+1.  pcin: channels of the projection input folded into this
 // layer as extra k-steps; pj: 1 = this conv1 also produces the block's projection (from its own input), 2 = this conv2
 // adds the produced projection (blocks 3 and 5: their block input is 4x / 2x wider than the block, so streaming it
-// again for a 1x1 convolution costs more HBM time than the layer's own work)
-const LayerCfg kLayers[10] = {
-    {32, 64, 0, 2, 1, 2, 1, 0},   {64, 64, 32, 2, 1, 2, 1, 0},      // bone/block1
-    {64, 128, 0, 4, 1, 1, 1, 0},  {128, 128, 64, 2, 2, 1, 2, 0},    // bone/block2
-    {128, 32, 0, 1, 2, 2, 1, 1},  {32, 32, 0, 1, 1, 4, 1, 2},       // value/block3
-    {128, 64, 0, 2, 2, 1, 1, 0},  {64, 64, 128, 2, 2, 1, 1, 0},     // policy/block4
-    {64, 32, 0, 1, 1, 4, 1, 1},   {32, 32, 0, 1, 1, 4, 1, 2},       // policy/block5
+// again for a 1x1 convolution costs more HBM time than the layer's own work) and ends its branch (fp32 planes or the fused head);
+// gy: workgroup kinds (blockIdx.y) of CT cout tiles each; xacc: a second accumulator set, wherever weights + 2 x accumulators +
+// fragments fit 512 registers
+constexpr LayerCfg kLayers[10] = {
+    {32, 64, 0, 2, 1, 2, 1, 0, true},    {64, 64, 32, 2, 1, 2, 1, 0, true},       // bone/block1
+    // (layer 2 as 2 workgroup kinds x (2 tiles, k-split, XACC): 1.605 vs 1.580 ms per forward, |dp| 1.23e-5 vs 1.28e-5)
+    {64, 128, 0, 4, 1, 1, 1, 0, false},  {128, 128, 64, 2, 2, 1, 2, 0, false},    // bone/block2
+    // (layer 4 without XACC: weights + projection weights + 3 accumulator sets would spill; layer 5: one pixel tile per wave, whole K:
+    //  no k-split exchange)
+    {128, 32, 0, 1, 2, 2, 1, 1, false},  {32, 32, 0, 1, 1, 4, 1, 2, true},        // value/block3
+    {128, 64, 0, 2, 2, 1, 1, 0, false},  {64, 64, 128, 2, 2, 1, 1, 0, true},      // policy/block4
+    {64, 32, 0, 1, 1, 4, 1, 1, true},    {32, 32, 0, 1, 1, 4, 1, 2, true},        // policy/block5
 };
 const char* const kBlockNames[5] = {"bone/block1", "bone/block2", "value/block3", "policy/block4", "policy/block5"};
+template <int LI> constexpr int kHeadOf = LI == 4 || LI == 5 ? 1 : LI == 8 || LI == 9 ? 2 : 0;   // the head blocks 3 / 5 can fuse: 1 value, 2 policy
 
-constexpr int kSmallBatch = 8;             // <= this many positions: a position's pixel tiles are split over workgroups (af_conv_f16s_sb)
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K, set once: the attribute belongs to the (function, device) pair, so each K has
+// one bit per device (a process may drive several GPUs, one handle each; handles are created on their own device and launched with it
+// current).  A launch function asks for its device's bit once and hands it to every dyn_lds it needs.
+int device_bit(uint64_t* bit) {
+    int dev = 0;
+    FS_HIP_OK(hipGetDevice(&dev));
+    *bit = 1ull << (dev & 63);
+    return 0;
+}
+template <auto K>
+int dyn_lds(uint64_t bit, int bytes) {
+    static std::atomic<uint64_t> devs{0};
+    if (!(devs.load(std::memory_order_relaxed) & bit)) {
+        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        devs.fetch_or(bit, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
+// tile_split (F16sPlan): a position's pixel tiles are split over workgroups (af_conv_f16s_sb)
 template <class G, int NSM, int NSP, int CT, int KS, int PS, bool OUT32, bool XACC, int PJ = 0, int HD = 0, int DIST = kDist, int WPE = 1>
-int launch_cfg(hipStream_t st, const F16sArgs& a, int gy, int ncu) {
+int launch_cfg(hipStream_t st, const F16sArgs& a, int gy, int ncu, bool tile_split) {
     constexpr int NT = 4 / PS;
     constexpr size_t lds = Lds<G, DIST>::kScrOff + (KS == 2 ? (size_t)CT * PS * NT * 4096 * (PJ == 1 ? 2 : 1) : 0);
     static_assert(WPE * lds <= 160 * 1024, "LDS budget of the workgroups sharing a CU");
 #ifndef AF_F16S_NO_LDS_ASSERT                    // (A/B builds with a deeper ring only fit the 11x11 geometry)
     static_assert(lds <= 160 * 1024, "LDS budget");
 #endif
-    // the attribute belongs to the (function, device) pair: one bit per device for this instantiation (a process may drive
-    // several GPUs, one handle each; handles are created on their own device and launched with it current)
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    FS_HIP_OK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_conv_f16s<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD, DIST, WPE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_devs.fetch_or(bit, std::memory_order_relaxed);
-    }
+    uint64_t bit;
+    if (device_bit(&bit) || dyn_lds<af_conv_f16s<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD, DIST, WPE>>(bit, 160 * 1024)) return -2;
     constexpr int NTS = KS == 2 ? 2 : 1;                                  // tiles per wave of the small-batch split
     if constexpr (NTS < NT && HD == 0) {
-        if (a.batch <= kSmallBatch && !(a.abl & 128)) {                    // (abl bit 7: the one-workgroup-per-position launch, for A/B)
-            static std::atomic<uint64_t> attr_sb{0};
-            if (!(attr_sb.load(std::memory_order_relaxed) & bit)) {
-                FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_conv_f16s_sb<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD, DIST, WPE, NTS>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_sb.fetch_or(bit, std::memory_order_relaxed);
-            }
+        if (tile_split) {
+            if (dyn_lds<af_conv_f16s_sb<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD, DIST, WPE, NTS>>(bit, 160 * 1024)) return -2;
             hipLaunchKernelGGL((af_conv_f16s_sb<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD, DIST, WPE, NTS>),
                                dim3(a.batch * G::HALVES, gy, NT / NTS), dim3(256), lds, st, a);
             FS_HIP_OK(hipGetLastError());
@@ -1804,24 +1816,19 @@ int launch_cfg(hipStream_t st, const F16sArgs& a, int gy, int ncu) {
     return 0;
 }
 
-// blocks 3 and 5 (11x11): both convolutions + the fused head in one launch (af_block_f16s)
-template <class G, int NSM, int KS, int PS, bool XACC, int FU>
+// blocks 3 and 5 (11x11; LI = 4 / 8, the block's first layer): both convolutions + the fused head in one launch (af_block_f16s)
+template <class G, int LI>
 int launch_block(hipStream_t st, const F16sArgs& a, int ncu) {
+    constexpr LayerCfg L = kLayers[LI];
+    constexpr int NSM = L.cin / 32, KS = L.KS, PS = L.PS, FU = kHeadOf<LI>;
     constexpr int DIST = 2;                       // (a 5-slot ring + the activation slab + 36 KB of second-layer weights exceed 160 KB)
     constexpr size_t scr = KS == 2 ? (size_t)PS * (4 / PS) * 4096 * 2 : 0;
     constexpr size_t lds = Lds<G, DIST>::kScrOff + (scr > Lay<G>::kSlotL ? scr : Lay<G>::kSlotL) + 36864;
     static_assert(lds <= 160 * 1024, "LDS budget of the fused block");
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    FS_HIP_OK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_block_f16s<G, NSM, KS, PS, XACC, FU, DIST>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_devs.fetch_or(bit, std::memory_order_relaxed);
-    }
+    uint64_t bit;
+    if (device_bit(&bit) || dyn_lds<af_block_f16s<G, NSM, KS, PS, L.xacc, FU, DIST>>(bit, 160 * 1024)) return -2;
     const int gx = std::max(1, std::min(a.batch, ncu));
-    hipLaunchKernelGGL((af_block_f16s<G, NSM, KS, PS, XACC, FU, DIST>), dim3(gx), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((af_block_f16s<G, NSM, KS, PS, L.xacc, FU, DIST>), dim3(gx), dim3(256), lds, st, a);
     FS_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -1831,15 +1838,8 @@ template <class G, int NSM, int NSP, int CT, int KS, bool XACC>
 int launch_h15(hipStream_t st, F16sArgs a, int gy, int ncu) {
     constexpr size_t lds = Lds<G, kDist>::kScrOff + (KS == 2 ? (size_t)CT * 4 * 4096 : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    FS_HIP_OK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_conv_f16s_h15<G, NSM, NSP, CT, KS, XACC>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_devs.fetch_or(bit, std::memory_order_relaxed);
-    }
+    uint64_t bit;
+    if (device_bit(&bit) || dyn_lds<af_conv_f16s_h15<G, NSM, NSP, CT, KS, XACC>>(bit, 160 * 1024)) return -2;
     // gx workgroups per blockIdx.y, split 9 : 7 between the 4-tile class (half 0) and the 3-tile class (half 1), each a multiple of 8
     // (4 x 28.4 = 114 against 3 x 36.6 = 110 tile passes per workgroup at 4096 boards on 144 + 112 workgroups)
     const int gx = std::max(16, ncu / gy / 16 * 16);
@@ -1886,7 +1886,6 @@ struct f16s_net {
     int* df = nullptr;            // af_small_forward_f16s: role counters (kDfWords ints, zero between launches)
     float* pfx = nullptr;         // ... and the policy head's K-half hand-over (16 KB)
     char* stash = nullptr;        // 15x15: corner operands of the layer in flight (af_conv_f16s_h15 -> af_corner_f16s), 6 slabs x 512 B per board
-    int abl = 0;
     std::vector<std::pair<const void*, size_t>> wreg;   // weight-derived buffers and their sizes, in f16s_weight_buffer's order
 };
 
@@ -2198,243 +2197,228 @@ int f16s_scales(const f16s_net* n, float* out, int cap) {
     return 25;
 }
 
-void f16s_set_ablation(f16s_net* n, int bits) { if (n) n->abl = bits; }
+// ------------------------------------------------------------ the launch plan ------------------------------------------------------------
+constexpr int kSmallBatch = 8;             // <= this many positions: the pixel-tile split, the small pair kernels, the single launch of roles
 
-// the ten layers on one board geometry.  <NSM, NSP, CT, KS, PS, OUT32, XACC[, PJ, HD]>: XACC wherever weights + 2 x accumulators +
-// fragments fit 512 registers; the fused head variants (HD = 1 value, 2 policy) are launched for both geometries
-template <class G>
-static int launch_layer_g(f16s_net* n, hipStream_t st, int li, const F16sArgs& a, int head) {
-    switch (li) {
-        // the three 32-channel-input layers (one slab per position): two workgroups per CU, prefetch distance 1 (abl bit 5 = the
-        // one-workgroup instantiation, for A/B)
-        // (11x11 only: two 3-slot rings of 20-KB slots + zero regions exceed 160 KB on 15x15)
-        case 0:
-            if constexpr (G::S == 11) { if (!(n->abl & 32)) return launch_cfg<G, 1, 0, 2, 1, 2, false, false, 0, 0, 1, 2>(st, a, 1, n->ncu); }   // (no XACC: 256 registers)
-            return launch_cfg<G, 1, 0, 2, 1, 2, false, true>(st, a, 1, n->ncu);
-        case 1: return launch_cfg<G, 2, 1, 2, 1, 2, false, true>(st, a, 1, n->ncu);
-        // 15x15 (r5): the four PS = 1 layers run the 4-tile / 3-tile half classes + the corner kernel (abl bit 6 = the r3 two-halves launch,
-        // for A/B; small batches keep it too: the class split assumes every workgroup has boards of its half)
-        case 2:
-            if constexpr (G::S == 15) { if (!(n->abl & 64) && a.batch >= 128) return launch_h15<G, 2, 0, 4, 1, false>(st, a, 1, n->ncu); }
-            return launch_cfg<G, 2, 0, 4, 1, 1, false, false>(st, a, 1, n->ncu);   // (as 2 workgroup kinds x (2 tiles, k-split, XACC): 1.605 vs 1.580 ms per forward, |dp| 1.23e-5 vs 1.28e-5)
-        case 3:
-            if constexpr (G::S == 15) { if (!(n->abl & 64) && a.batch >= 128) return launch_h15<G, 4, 2, 2, 2, false>(st, a, 2, n->ncu); }
-            return launch_cfg<G, 4, 2, 2, 2, 1, false, false>(st, a, 2, n->ncu);
-        case 4: return launch_cfg<G, 4, 0, 1, 2, 2, false, false, 1>(st, a, 1, n->ncu);   // (no XACC: weights + projection weights + 3 accumulator sets would spill)
-        case 5:                                                                           // (one pixel tile per wave, whole K: no k-split exchange)
-            if constexpr (G::S == 11) { if (head == 0 && !(n->abl & 32)) return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2, 1, 1, 2>(st, a, 1, n->ncu); }
-            if (head == 0) return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2, 1>(st, a, 1, n->ncu);
-            return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2>(st, a, 1, n->ncu);
-        case 6:
-            if constexpr (G::S == 15) { if (!(n->abl & 64) && a.batch >= 128) return launch_h15<G, 4, 0, 2, 2, false>(st, a, 1, n->ncu); }
-            return launch_cfg<G, 4, 0, 2, 2, 1, false, false>(st, a, 1, n->ncu);
-        case 7:
-            if constexpr (G::S == 15) { if (!(n->abl & 64) && a.batch >= 128) return launch_h15<G, 2, 4, 2, 2, true>(st, a, 1, n->ncu); }
-            return launch_cfg<G, 2, 4, 2, 2, 1, false, true>(st, a, 1, n->ncu);
-        case 8: return launch_cfg<G, 2, 0, 1, 1, 4, false, true, 1>(st, a, 1, n->ncu);
-        default:
-            if constexpr (G::S == 11) { if (head == 1 && !(n->abl & 32)) return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2, 2, 1, 2>(st, a, 1, n->ncu); }
-            if (head == 1) return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2, 2>(st, a, 1, n->ncu);
-            return launch_cfg<G, 1, 0, 1, 1, 4, true, true, 2>(st, a, 1, n->ncu);
-    }
+// Every test of the batch size and of the af_net_tune key-7 bits (F16sBits) that chooses between launch variants is made here.
+F16sPlan f16s_plan(const f16s_net* n, int batch, int bits, bool heads) {
+    const bool s11 = n->S == 11, small = batch <= kSmallBatch;
+    F16sPlan p = {};
+    p.batch = batch; p.bits = bits; p.heads = heads;
+    p.valu_stem = bits & kF16sValuStem;
+    // the three 32-channel-input layers (one slab per position): two workgroups per CU, prefetch distance 1
+    // (11x11 only: two 3-slot rings of 20-KB slots + zero regions exceed 160 KB on 15x15)
+    p.two_wg_per_cu = s11 && !(bits & kF16sOneWgPerCu);
+    // 15x15 (r5): the four PS = 1 layers run the 4-tile / 3-tile half classes + the corner kernel (small batches keep the r3 two-halves
+    // launch: the class split assumes every workgroup has boards of its half)
+    p.half_classes = !s11 && batch >= 128 && !(bits & kF16sTwoHalves15);
+    p.tile_split = small && !(bits & kF16sWgPerPosition);
+    p.fused_blocks = s11 && heads && !(bits & kF16sTwoLaunchBlocks);
+    if (p.fused_blocks && p.tile_split && p.two_wg_per_cu && !p.valu_stem && !(bits & (kF16sBranchLaunchesSmall | kF16sLaunchSequence)))
+        p.form = kF16sRoles;            // (the roles are the default variants' bodies: the form yields to every older A/B bit of the small-batch path)
+    else if (p.fused_blocks && (small ? p.tile_split && !(bits & kF16sBranchLaunchesSmall) : !(bits & kF16sBranchLaunchesBig)))
+        p.form = kF16sPaired;           // (af_small_pair_f16s / af_small_l7v_f16s hold the tile-split bodies, af_big_* the whole-position ones)
+    else
+        p.form = kF16sBranches;
+    return p;
 }
 
-static int launch_layer(f16s_net* n, hipStream_t st, int li, const char* in, const char* in2, char* out, float* out32, int batch,
-                        int WP, int PP, int head = -1) {
-    F16sArgs a;
-    a.hw = nullptr; a.hbias = nullptr; a.hx = nullptr; a.inv_scale_h = 1.0f;
-    if (head >= 0) { a.hw = n->hcw[head]; a.hbias = n->hcb[head]; a.hx = n->hx[head]; a.inv_scale_h = n->hc_inv[head]; }
-    a.in = in; a.in2 = in2; a.w = n->w[li]; a.bias = n->bias[li]; a.out = out; a.out32 = out32;
-    a.inv_scale = n->inv_scale[li]; a.batch = batch; a.WP = WP; a.PP = PP; a.abl = (n->abl & 0xf0ff) | (li << 8); a.gx0 = 0; a.stash = n->stash;
-    {   // profiling only: AF_F16S_ABL_LAYERS = bit mask of the layers the traffic-ablation bits (1, 2, 4, 8, 4096) apply to (default: all)
-        static const int mask = [] { const char* e = getenv("AF_F16S_ABL_LAYERS"); return e ? (int)strtol(e, nullptr, 0) : 0x3ff; }();
-        if (!((mask >> li) & 1)) a.abl &= ~0x100f;
-    }
-    a.w2 = nullptr; a.bias2 = nullptr; a.inv_scale2 = 1.0f;
+// The one place an F16sArgs is made: what depends on (n, plan, layer) only.  Everything else is null / 0 and inv_scale2 = inv_scale_h = 1;
+// callers add the data pointers, the second convolution of a fused block (add_conv2) and the fused head (add_head).  pw and pbuf are
+// null wherever the layer neither produces nor consumes a projection (f16s_create allocates them for pj == 1 only).
+static F16sArgs layer_args(const f16s_net* n, const F16sPlan& p, int li, const char* in, const char* in2, char* out) {
+    F16sArgs a = {};
+    a.in = in; a.in2 = in2; a.out = out;
+    a.w = n->w[li]; a.bias = n->bias[li]; a.inv_scale = n->inv_scale[li];
     a.pw = n->pw[li]; a.pbuf = n->pbuf[li / 2]; a.inv_scale_p = n->inv_scale_p[li];
-    return n->S == 11 ? launch_layer_g<Geo<11>>(n, st, li, a, head) : launch_layer_g<Geo<15>>(n, st, li, a, head);
+    a.inv_scale2 = a.inv_scale_h = 1.0f;
+    a.batch = p.batch; a.stash = n->stash;
+    a.abl = (p.bits & 0xf0ff) | (li << 8);
+    // profiling only: AF_F16S_ABL_LAYERS = bit mask of the layers the traffic-ablation bits apply to (default: all)
+    static const int mask = [] { const char* e = getenv("AF_F16S_ABL_LAYERS"); return e ? (int)strtol(e, nullptr, 0) : 0x3ff; }();
+    if (!((mask >> li) & 1)) a.abl &= ~kF16sProfilingBits;
+    return a;
 }
-
-int f16s_trunk(f16s_net* n, hipStream_t st, const float* planes, int batch) {
-    if (!n || batch < 1 || batch > n->max_batch) return -1;
-    if (n->abl & 16) {       // A/B: the VALU stem
-        if (n->S == 15) hipLaunchKernelGGL(af_stem_f16s<Geo<15>>, dim3(std::min(batch, 2048)), dim3(256), 0, st, planes, n->stem_w, n->stem_b, n->f0, batch);
-        else hipLaunchKernelGGL(af_stem_f16s<Geo<11>>, dim3(std::min(batch, 2048)), dim3(256), 0, st, planes, n->stem_w, n->stem_b, n->f0, batch);
-    } else if (n->S == 15) {
-        hipLaunchKernelGGL(af_stem_mfma_f16s<Geo<15>>, dim3(std::min(batch, 1024)), dim3(256), 0, st, planes, n->stem_wm, n->stem_b, n->stem_inv_scale,
-                           n->f0, batch);
-    } else {
-        hipLaunchKernelGGL(af_stem_mfma_f16s<Geo<11>>, dim3(std::min(batch, 1024)), dim3(256), 0, st, planes, n->stem_wm, n->stem_b, n->stem_inv_scale,
-                           n->f0, batch);
-    }
-    int rc = launch_layer(n, st, 0, n->f0, nullptr, n->g[0], nullptr, batch, 0, 0);
-    if (!rc) rc = launch_layer(n, st, 1, n->g[0], n->f0, n->o[0], nullptr, batch, 0, 0);
-    if (!rc) rc = launch_layer(n, st, 2, n->o[0], nullptr, n->g[1], nullptr, batch, 0, 0);
-    if (!rc) rc = launch_layer(n, st, 3, n->g[1], n->o[0], n->o[1], nullptr, batch, 0, 0);
-    return rc;
-}
-
-// F16sArgs of a fused block: the first convolution's (layer li) + the second one's weights / bias / scale + the head's
-static F16sArgs block_args(f16s_net* n, int li, const char* in, int batch, int head) {
-    F16sArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in; a.w = n->w[li]; a.bias = n->bias[li]; a.inv_scale = n->inv_scale[li];
-    a.pw = n->pw[li]; a.inv_scale_p = n->inv_scale_p[li];
-    a.w2 = n->w[li + 1]; a.bias2 = n->bias[li + 1]; a.inv_scale2 = n->inv_scale[li + 1];
-    a.hw = n->hcw[head]; a.hbias = n->hcb[head]; a.hx = n->hx[head]; a.inv_scale_h = n->hc_inv[head];
-    a.batch = batch; a.abl = (n->abl & 0xf0ff) | (li << 8); a.stash = n->stash;
+static void add_conv2(F16sArgs& a, const f16s_net* n, int li) { a.w2 = n->w[li]; a.bias2 = n->bias[li]; a.inv_scale2 = n->inv_scale[li]; }
+static void add_head(F16sArgs& a, const f16s_net* n, int h) { a.hw = n->hcw[h]; a.hbias = n->hcb[h]; a.hx = n->hx[h]; a.inv_scale_h = n->hc_inv[h]; }
+// F16sArgs of a fused block: the first convolution's (layer LI = 4 / 8) + the second one's weights / bias / scale + the head's
+template <int LI>
+static F16sArgs block_args(const f16s_net* n, const F16sPlan& p, const char* in) {
+    F16sArgs a = layer_args(n, p, LI, in, nullptr, nullptr);
+    add_conv2(a, n, LI + 1);
+    add_head(a, n, kHeadOf<LI> - 1);
     return a;
 }
 
-int f16s_value_branch(f16s_net* n, hipStream_t st, int batch, float* o3, int WP, int PP, float* value) {
+// the kernels other than the convolutions are instantiated per geometry only: f(Geo<S>{})
+template <class F>
+static int with_geo(const f16s_net* n, F&& f) { return n->S == 11 ? f(Geo<11>{}) : f(Geo<15>{}); }
+
+// Layer LI on geometry G: every template argument that restates kLayers[LI] is derived from it.  What is written out below are the real
+// choices between instantiations of one layer.
+template <class G, int LI>
+static int launch_one(const f16s_net* n, const F16sPlan& p, hipStream_t st, const F16sArgs& a) {
+    constexpr LayerCfg L = kLayers[LI];
+    constexpr int NSM = L.cin / 32, NSP = L.pcin / 32, CT = L.CT, KS = L.KS, PS = L.PS, PJ = L.pj, HD = kHeadOf<LI>;
+    constexpr bool OUT32 = PJ == 2, XACC = L.xacc;
+    const bool head = OUT32 && p.heads;                    // the fused head variants (HD = 1 value, 2 policy) are launched for both geometries
+    // layers 0, 5 and 9 on 11x11 (F16sPlan::two_wg_per_cu): DIST = 1, WPE = 2; layer 0 then without XACC (256 registers); layers 5 and 9
+    // only with their head
+    if constexpr (G::S == 11 && (LI == 0 || LI == 5 || LI == 9)) {
+        if (p.two_wg_per_cu && (head || !OUT32))
+            return launch_cfg<G, NSM, NSP, CT, KS, PS, OUT32, XACC && LI != 0, PJ, HD, 1, 2>(st, a, L.gy, n->ncu, p.tile_split);
+    }
+    // layers 2, 3, 6 and 7 on 15x15 (F16sPlan::half_classes)
+    if constexpr (G::S == 15 && (LI == 2 || LI == 3 || LI == 6 || LI == 7)) {
+        if (p.half_classes) return launch_h15<G, NSM, NSP, CT, KS, XACC>(st, a, L.gy, n->ncu);
+    }
+    if constexpr (OUT32) {
+        if (head) return launch_cfg<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ, HD>(st, a, L.gy, n->ncu, p.tile_split);
+    }
+    return launch_cfg<G, NSM, NSP, CT, KS, PS, OUT32, XACC, PJ>(st, a, L.gy, n->ncu, p.tile_split);
+}
+// the last layer of a branch (LI = 5 / 9) writes fp32 planes out32, or with p.heads the head's dense input
+template <int LI>
+static int launch_layer(const f16s_net* n, const F16sPlan& p, hipStream_t st, const char* in, const char* in2, char* out,
+                        float* out32 = nullptr, int WP = 0, int PP = 0) {
+    F16sArgs a = layer_args(n, p, LI, in, in2, out);
+    a.out32 = out32; a.WP = WP; a.PP = PP;
+    if constexpr (kLayers[LI].pj == 2) {
+        if (p.heads) add_head(a, n, kHeadOf<LI> - 1);
+    }
+    return with_geo(n, [&](auto g) { return launch_one<decltype(g), LI>(n, p, st, a); });
+}
+static int launch_policy_fc(const f16s_net* n, hipStream_t st, int batch, float* policy) {
+    return with_geo(n, [&](auto g) {
+        hipLaunchKernelGGL(af_policy_fc_f16s<decltype(g)>, dim3((batch + kPfPos - 1) / kPfPos), dim3(512), kPfLds, st, n->hx[1], n->hfw[1], n->hfb[1],
+                           n->hf_inv[1], policy, batch);
+        return 0;
+    });
+}
+
+int f16s_trunk(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes) {
+    const int batch = p.batch;
+    if (!n || batch < 1 || batch > n->max_batch) return -1;
+    with_geo(n, [&](auto g) {
+        using G = decltype(g);
+        if (p.valu_stem) hipLaunchKernelGGL(af_stem_f16s<G>, dim3(std::min(batch, 2048)), dim3(256), 0, st, planes, n->stem_w, n->stem_b, n->f0, batch);
+        else hipLaunchKernelGGL(af_stem_mfma_f16s<G>, dim3(std::min(batch, 1024)), dim3(256), 0, st, planes, n->stem_wm, n->stem_b, n->stem_inv_scale, n->f0, batch);
+        return 0;
+    });
+    int rc = launch_layer<0>(n, p, st, n->f0, nullptr, n->g[0]);
+    if (!rc) rc = launch_layer<1>(n, p, st, n->g[0], n->f0, n->o[0]);
+    if (!rc) rc = launch_layer<2>(n, p, st, n->o[0], nullptr, n->g[1]);
+    if (!rc) rc = launch_layer<3>(n, p, st, n->g[1], n->o[0], n->o[1]);
+    return rc;
+}
+
+int f16s_value_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o3, int WP, int PP, float* value) {
     int rc;
-    if (n->S == 11 && value && !(n->abl & 256)) {          // (abl bit 8: the two-launch block, for A/B)
-        rc = launch_block<Geo<11>, 4, 2, 2, false, 1>(st, block_args(n, 4, n->o[1], batch, 0), n->ncu);
+    if (p.fused_blocks) {
+        rc = launch_block<Geo<11>, 4>(st, block_args<4>(n, p, n->o[1]), n->ncu);
     } else {
-        rc = launch_layer(n, st, 4, n->o[1], nullptr, n->g[2], nullptr, batch, 0, 0);
-        if (!rc) rc = launch_layer(n, st, 5, n->g[2], n->o[1], nullptr, o3, batch, WP, PP, value ? 0 : -1);
+        rc = launch_layer<4>(n, p, st, n->o[1], nullptr, n->g[2]);
+        if (!rc) rc = launch_layer<5>(n, p, st, n->g[2], n->o[1], nullptr, o3, WP, PP);
     }
-    if (!rc && value) {
-        if (n->S == 11)
-            hipLaunchKernelGGL(af_value_fc_f16s<Geo<11>>, dim3((batch + 31) / 32), dim3(128), 0, st, n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b,
-                               n->hf_inv[0], value, batch);
-        else
-            hipLaunchKernelGGL(af_value_fc_f16s<Geo<15>>, dim3((batch + 31) / 32), dim3(128), 0, st, n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b,
-                               n->hf_inv[0], value, batch);
-    }
+    if (!rc && p.heads)
+        with_geo(n, [&](auto g) {
+            hipLaunchKernelGGL(af_value_fc_f16s<decltype(g)>, dim3((p.batch + 31) / 32), dim3(128), 0, st, n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b,
+                               n->hf_inv[0], value, p.batch);
+            return 0;
+        });
     return rc;
 }
 
-int f16s_policy_branch(f16s_net* n, hipStream_t st, int batch, float* o5, int WP, int PP, float* policy) {
-    int rc = launch_layer(n, st, 6, n->o[1], nullptr, n->g[3], nullptr, batch, 0, 0);
-    if (!rc) rc = launch_layer(n, st, 7, n->g[3], n->o[1], n->o[3], nullptr, batch, 0, 0);
-    if (!rc && n->S == 11 && policy && !(n->abl & 256)) {
-        rc = launch_block<Geo<11>, 2, 1, 4, true, 2>(st, block_args(n, 8, n->o[3], batch, 1), n->ncu);
+int f16s_policy_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o5, int WP, int PP, float* policy) {
+    int rc = launch_layer<6>(n, p, st, n->o[1], nullptr, n->g[3]);
+    if (!rc) rc = launch_layer<7>(n, p, st, n->g[3], n->o[1], n->o[3]);
+    if (!rc && p.fused_blocks) {
+        rc = launch_block<Geo<11>, 8>(st, block_args<8>(n, p, n->o[3]), n->ncu);
     } else {
-        if (!rc) rc = launch_layer(n, st, 8, n->o[3], nullptr, n->g[4], nullptr, batch, 0, 0);
-        if (!rc) rc = launch_layer(n, st, 9, n->g[4], n->o[3], nullptr, o5, batch, WP, PP, policy ? 1 : -1);
+        if (!rc) rc = launch_layer<8>(n, p, st, n->o[3], nullptr, n->g[4]);
+        if (!rc) rc = launch_layer<9>(n, p, st, n->g[4], n->o[3], nullptr, o5, WP, PP);
     }
-    if (!rc && policy) {
-        if (n->S == 11)
-            hipLaunchKernelGGL(af_policy_fc_f16s<Geo<11>>, dim3((batch + kPfPos - 1) / kPfPos), dim3(512), kPfLds, st, n->hx[1], n->hfw[1], n->hfb[1],
-                               n->hf_inv[1], policy, batch);
-        else
-            hipLaunchKernelGGL(af_policy_fc_f16s<Geo<15>>, dim3((batch + kPfPos - 1) / kPfPos), dim3(512), kPfLds, st, n->hx[1], n->hfw[1], n->hfb[1],
-                               n->hf_inv[1], policy, batch);
-    }
+    if (!rc && p.heads) launch_policy_fc(n, st, p.batch, policy);
     return rc;
 }
 
-// Small batches on 11x11 (heads fused): both branches on ONE stream — {policy conv1 || value block} as one launch, the value head's
+// kF16sPaired (11x11, heads fused): both branches on ONE stream — {policy conv1 || value block} as one launch, the value head's
 // dense layers, then the rest of the policy branch.  The same kernels' bodies with the same arguments: the same bits.
-int f16s_small_branches(f16s_net* n, hipStream_t st, int batch, float* value, float* policy) {
-    if (!n || n->S != 11 || batch < 1 || !value || !policy) return -1;
+static int paired_branches(f16s_net* n, const F16sPlan& p, hipStream_t st, float* value, float* policy) {
     using G = Geo<11>;
-    const bool small = batch <= kSmallBatch;
-    F16sArgs P;
-    memset(&P, 0, sizeof(P));
-    P.in = n->o[1]; P.w = n->w[6]; P.bias = n->bias[6]; P.out = n->g[3]; P.inv_scale = n->inv_scale[6];
-    P.batch = batch; P.abl = (n->abl & 0xf0ff) | (6 << 8); P.stash = n->stash; P.inv_scale2 = 1.0f; P.inv_scale_h = 1.0f;
-    const F16sArgs V = block_args(n, 4, n->o[1], batch, 0);
+    const int batch = p.batch;
+    F16sArgs P = layer_args(n, p, 6, n->o[1], nullptr, n->g[3]);
+    const F16sArgs V = block_args<4>(n, p, n->o[1]);
     constexpr size_t ldsP = Lds<G, kDist>::kScrOff + (size_t)2 * 1 * 4 * 4096;                       // CT = 2, PS = 1, NTW = 4 (2 at small batches)
     constexpr size_t ldsV = Lds<G, 2>::kScrOff + (size_t)2 * 2 * 4096 * 2 + 36864;
     constexpr size_t lds = ldsP > ldsV ? ldsP : ldsV;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    FS_HIP_OK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_small_pair_f16s<G>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_big_pair_f16s<G>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_devs.fetch_or(bit, std::memory_order_relaxed);
-    }
+    uint64_t bit;
+    if (device_bit(&bit)) return -2;
     const int gp = std::max(1, std::min(batch, n->ncu));          // workgroups of a class at full batch: one per CU
-    if (small) {
+    if (p.tile_split) {
+        if (dyn_lds<af_small_pair_f16s<G>>(bit, 160 * 1024)) return -2;
         hipLaunchKernelGGL(af_small_pair_f16s<G>, dim3(3 * batch), dim3(256), lds, st, P, V);
     } else {
+        if (dyn_lds<af_big_pair_f16s<G>>(bit, 160 * 1024)) return -2;
         P.gx0 = gp;
         hipLaunchKernelGGL(af_big_pair_f16s<G>, dim3(2 * gp), dim3(256), lds, st, P, V);
     }
     FS_HIP_OK(hipGetLastError());
-    {
-        F16sArgs Q;
-        memset(&Q, 0, sizeof(Q));
-        Q.in = n->g[3]; Q.in2 = n->o[1]; Q.w = n->w[7]; Q.bias = n->bias[7]; Q.out = n->o[3]; Q.inv_scale = n->inv_scale[7];
-        Q.batch = batch; Q.abl = (n->abl & 0xf0ff) | (7 << 8); Q.stash = n->stash; Q.inv_scale2 = 1.0f; Q.inv_scale_h = 1.0f;
-        const VfcArgs F = {n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b, n->hf_inv[0], value};
-        constexpr size_t lds7 = Lds<G, kDist>::kScrOff + (size_t)2 * 1 * 4 * 4096;
-        static std::atomic<uint64_t> attr7{0};
-        if (!(attr7.load(std::memory_order_relaxed) & bit)) {
-            // (the kernels also have 256 bytes of static LDS — the value head's reduction buffer: dynamic + static must stay within 160 KB)
-            FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_small_l7v_f16s<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7));
-            FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_big_l7v_f16s<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7));
-            attr7.fetch_or(bit, std::memory_order_relaxed);
-        }
-        if (small) {
-            hipLaunchKernelGGL(af_small_l7v_f16s<G>, dim3(2 * batch + 1), dim3(256), lds7, st, Q, F);
-        } else {
-            Q.gx0 = gp;
-            hipLaunchKernelGGL(af_big_l7v_f16s<G>, dim3(gp + (batch + 31) / 32), dim3(256), lds7, st, Q, F);
-        }
-        FS_HIP_OK(hipGetLastError());
+    F16sArgs Q = layer_args(n, p, 7, n->g[3], n->o[1], n->o[3]);
+    const VfcArgs F = {n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b, n->hf_inv[0], value};
+    // (the kernels also have 256 bytes of static LDS — the value head's reduction buffer: dynamic + static must stay within 160 KB)
+    constexpr size_t lds7 = Lds<G, kDist>::kScrOff + (size_t)2 * 1 * 4 * 4096;
+    if (p.tile_split) {
+        if (dyn_lds<af_small_l7v_f16s<G>>(bit, (int)lds7)) return -2;
+        hipLaunchKernelGGL(af_small_l7v_f16s<G>, dim3(2 * batch + 1), dim3(256), lds7, st, Q, F);
+    } else {
+        if (dyn_lds<af_big_l7v_f16s<G>>(bit, (int)lds7)) return -2;
+        Q.gx0 = gp;
+        hipLaunchKernelGGL(af_big_l7v_f16s<G>, dim3(gp + (batch + 31) / 32), dim3(256), lds7, st, Q, F);
     }
-    int rc = launch_block<G, 2, 1, 4, true, 2>(st, block_args(n, 8, n->o[3], batch, 1), n->ncu);
-    if (!rc) hipLaunchKernelGGL(af_policy_fc_f16s<G>, dim3((batch + kPfPos - 1) / kPfPos), dim3(512), kPfLds, st, n->hx[1], n->hfw[1], n->hfb[1],
-                                n->hf_inv[1], policy, batch);
+    FS_HIP_OK(hipGetLastError());
+    const int rc = launch_block<G, 8>(st, block_args<8>(n, p, n->o[3]), n->ncu);
+    if (!rc) launch_policy_fc(n, st, batch, policy);
     FS_HIP_OK(hipGetLastError());
     return rc;
 }
 
-// The single-launch small-batch forward (af_small_forward_f16s) + the policy head's dense layer.
-// (abl bit 11 = the multi-launch form, for A/B; it also yields to the older A/B bits of the small-batch path)
-int f16s_small_forward_ok(const f16s_net* n, int batch) {
-    return n && n->S == 11 && batch >= 1 && batch <= kSmallBatch && !(n->abl & (16 | 32 | 128 | 256 | 512 | 2048));
-}
-static F16sArgs layer_args(f16s_net* n, int li, const char* in, const char* in2, char* out, int batch) {
-    F16sArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in; a.in2 = in2; a.w = n->w[li]; a.bias = n->bias[li]; a.out = out; a.inv_scale = n->inv_scale[li]; a.batch = batch;
-    a.abl = (n->abl & 0xf0ff) | (li << 8); a.stash = n->stash; a.inv_scale2 = 1.0f; a.inv_scale_h = 1.0f;
-    a.pw = n->pw[li]; a.pbuf = n->pbuf[li / 2]; a.inv_scale_p = n->inv_scale_p[li];
-    return a;
-}
-int f16s_small_forward(f16s_net* n, hipStream_t st, const float* planes, int batch, float* value, float* policy) {
-    if (!f16s_small_forward_ok(n, batch) || !planes || !value || !policy) return -1;
+// kF16sRoles: the single-launch small-batch forward (af_small_forward_f16s) + the policy head's dense layer
+static int roles_forward(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes, float* value, float* policy) {
     using G = Geo<11>;
-    SmallFwdArgs S;
-    memset(&S, 0, sizeof(S));
+    const int batch = p.batch;
+    SmallFwdArgs S = {};
     S.planes = planes; S.stem_w = n->stem_wm; S.stem_b = n->stem_b; S.stem_inv = n->stem_inv_scale; S.f0 = n->f0;
     S.df = n->df; S.batch = batch;
     auto role = [&](F16sArgs a, int wait, int need, int done) { a.df_wait = n->df + wait; a.df_need = need; a.df_done = n->df + done; a.df_err = n->df + kDfErr; return a; };
-    S.L0 = role(layer_args(n, 0, n->f0, nullptr, n->g[0], batch), kDfStem, 1, kDfL0);
-    S.L1 = role(layer_args(n, 1, n->g[0], n->f0, n->o[0], batch), kDfL0, 2, kDfL1);
-    S.L2 = role(layer_args(n, 2, n->o[0], nullptr, n->g[1], batch), kDfL1, 2, kDfL2);
-    S.L3 = role(layer_args(n, 3, n->g[1], n->o[0], n->o[1], batch), kDfL2, 4, kDfL3);
-    S.P = role(layer_args(n, 6, n->o[1], nullptr, n->g[3], batch), kDfL3, 4, kDfP);
-    S.P.pw = nullptr; S.P.pbuf = nullptr;
-    S.V = role(block_args(n, 4, n->o[1], batch, 0), kDfL3, 4, kDfV);
-    S.Q = role(layer_args(n, 7, n->g[3], n->o[1], n->o[3], batch), kDfP, 2, kDfQ);
-    S.Q.pw = nullptr; S.Q.pbuf = nullptr;
-    S.B5 = role(block_args(n, 8, n->o[3], batch, 1), kDfQ, 2, kDfB5);
+    S.L0 = role(layer_args(n, p, 0, n->f0, nullptr, n->g[0]), kDfStem, 1, kDfL0);
+    S.L1 = role(layer_args(n, p, 1, n->g[0], n->f0, n->o[0]), kDfL0, 2, kDfL1);
+    S.L2 = role(layer_args(n, p, 2, n->o[0], nullptr, n->g[1]), kDfL1, 2, kDfL2);
+    S.L3 = role(layer_args(n, p, 3, n->g[1], n->o[0], n->o[1]), kDfL2, 4, kDfL3);
+    S.P = role(layer_args(n, p, 6, n->o[1], nullptr, n->g[3]), kDfL3, 4, kDfP);
+    S.V = role(block_args<4>(n, p, n->o[1]), kDfL3, 4, kDfV);
+    S.Q = role(layer_args(n, p, 7, n->g[3], n->o[1], n->o[3]), kDfP, 2, kDfQ);
+    S.B5 = role(block_args<8>(n, p, n->o[3]), kDfQ, 2, kDfB5);
     S.F = VfcArgs{n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b, n->hf_inv[0], value};
     constexpr size_t ldsC = Lds<G, kDist>::kScrOff + (size_t)2 * 1 * 4 * 4096;                 // the k-split layers (CT = 2, PS = 1)
     constexpr size_t ldsV = Lds<G, 2>::kScrOff + (size_t)2 * 2 * 4096 * 2 + 36864;           // the value block
     constexpr size_t ldsB = Lds<G, 2>::kScrOff + Lay<G>::kSlotL + 36864;                     // block 5
     constexpr size_t lds = std::max(std::max(ldsC, ldsV), std::max(ldsB, (size_t)StemLds<G>::kBytes));
     static_assert(lds + 256 <= 160 * 1024, "LDS budget (dynamic + the value head's static reduction buffer)");
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    FS_HIP_OK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-        FS_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_small_forward_f16s<G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_devs.fetch_or(bit, std::memory_order_relaxed);
-    }
+    uint64_t bit;
+    if (device_bit(&bit) || dyn_lds<af_small_forward_f16s<G>>(bit, (int)lds)) return -2;
     S.xp = n->hx[1]; S.pfa = n->hfw[1]; S.pfb = n->hfb[1]; S.pf_inv = n->hf_inv[1]; S.policy = policy; S.pfx = n->pfx;
     hipLaunchKernelGGL(af_small_forward_f16s<G>, dim3(19 * batch + 3), dim3(256), lds, st, S);
     FS_HIP_OK(hipGetLastError());
     return 0;
+}
+
+int f16s_forward(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes, float* value, float* policy) {
+    if (!n || p.form == kF16sBranches || p.batch < 1 || p.batch > n->max_batch || !planes || !value || !policy) return -1;
+    if (p.form == kF16sRoles) return roles_forward(n, p, st, planes, value, policy);
+    const int rc = f16s_trunk(n, p, st, planes);
+    return rc ? rc : paired_branches(n, p, st, value, policy);
 }
 // 1 if a role of af_small_forward_f16s ever gave up waiting (synchronises; tests)
 int f16s_small_forward_error(f16s_net* n) {
@@ -2443,11 +2427,6 @@ int f16s_small_forward_error(f16s_net* n) {
     FS_HIP_OK(hipDeviceSynchronize());
     FS_HIP_OK(hipMemcpy(&e, n->df + kDfErr, sizeof(int), hipMemcpyDeviceToHost));
     return e;
-}
-// (abl bit 9: the two-stream form at small batches; bit 10: at full batch — for A/B)
-int f16s_small_branches_ok(const f16s_net* n, int batch) {
-    if (!n || n->S != 11 || (n->abl & 256)) return 0;
-    return batch <= kSmallBatch ? !(n->abl & (128 | 512)) : !(n->abl & 1024);
 }
 
 // debug / tests: activation `which` (0 f0, 1 g1, 2 o1, 3 g2, 4 o2, 5 g3, 6 g4, 7 o4, 8 g5) of the first `batch` positions as

@@ -910,28 +910,21 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
     for (int i = 0; i < 5; ++i) { g[i] = n->g[i] + po * kBlocks[i].cout; o[i] = n->o[i] + po * kBlocks[i].cout; }
     const bool split16 = g_wino == 5 && n->f16s != nullptr;     // (board sizes without the split-operand path run the fp32 Winograd path)
     const bool fhead = split16 && g_fhead;                 // heads fused into the split-operand path
+    F16sPlan plan = {};
     if (split16) {
-        f16s_set_ablation(n->f16s, g_f16s_abl);
-        if (fhead && f16s_small_forward_ok(n->f16s, batch)) {
-            // <= 8 positions on 11x11: one launch of dataflow roles instead of nine dependent launches (af_conv_f16s.hip, r6)
-            if (f16s_small_forward(n->f16s, st, planes, batch, value, policy)) return AF_NET_ERR_HIP;
-            return AF_NET_OK;
-        }
-        if (f16s_trunk(n->f16s, st, planes, batch)) return AF_NET_ERR_HIP;
+        plan = f16s_plan(n->f16s, batch, g_f16s_abl, fhead);
+        // 11x11 with fused heads: <= 8 positions as one launch of dataflow roles instead of nine dependent launches (r6); otherwise the
+        // trunk, then both branches paired on this stream (fork and join of a side stream cost more than the value branch's kernels)
+        if (plan.form != kF16sBranches) return f16s_forward(n->f16s, plan, st, planes, value, policy) ? AF_NET_ERR_HIP : AF_NET_OK;
+        if (f16s_trunk(n->f16s, plan, st, planes)) return AF_NET_ERR_HIP;
     } else {
         hipLaunchKernelGGL(af_stem_conv, dim3(batch), dim3(256), 0, st, planes, n->stem_w, n->stem_b, f0, S, WP, PP);
-    }
-    if (fhead && f16s_small_branches_ok(n->f16s, batch)) {
-        // small batches: fork and join of the value branch's side stream cost more than its kernels (af_conv_f16s.hip)
-        if (f16s_small_branches(n->f16s, st, batch, value, policy)) return AF_NET_ERR_HIP;
-        NET_HIP_OK(hipGetLastError());
-        return AF_NET_OK;
     }
     const float* block_in[5] = {f0, o[0], o[1], o[1], o[3]};
     // the value branch (block3 + head) only depends on the trunk output o[1]: it runs on a side stream,
     // concurrently with the policy branch (blocks 4,5 + head), filling the SIMDs the 32/64-wide layers leave idle
     // (r5: on the split-operand path the side stream is used by neither board size any more — 11x11 runs the value branch as workgroup
-    //  classes of the policy branch's launches (f16s_small_branches above); 15x15 serialised is 0.7 % faster than forked, 2.653 vs 2.672 ms:
+    //  classes of the policy branch's launches (kF16sPaired above); 15x15 serialised is 0.7 % faster than forked, 2.653 vs 2.672 ms:
     //  fork and join cost more than the tail filling returns.  af_net_tune(4, 2) forces the side stream for A/B.)
     hipStream_t vs = st;
     if (g_branch && n->branch_stream && (!split16 || g_branch == 2)) {
@@ -946,8 +939,8 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
         }
         hipStream_t st = (i == 2) ? vs : st_main;
         if (split16) {
-            if (i == 2 && f16s_value_branch(n->f16s, st, batch, o[2], WP, PP, fhead ? value : nullptr)) return AF_NET_ERR_HIP;
-            if (i == 4 && f16s_policy_branch(n->f16s, st, batch, o[4], WP, PP, fhead ? policy : nullptr)) return AF_NET_ERR_HIP;
+            if (i == 2 && f16s_value_branch(n->f16s, plan, st, o[2], WP, PP, value)) return AF_NET_ERR_HIP;
+            if (i == 4 && f16s_policy_branch(n->f16s, plan, st, o[4], WP, PP, policy)) return AF_NET_ERR_HIP;
         } else {
             // conv1 3x3 + ELU (network.py:54); conv2 3x3 (+) 1x1 projection, add, ELU (network.py:53,55,56)
             launch_wino(st, n, batch, block_in[i], n->wino1_u[i], b.cin, nullptr, nullptr, 0, n->conv1_b[i], g[i], b.cout);
@@ -996,7 +989,7 @@ int af_net_tune(int32_t key, int32_t value) {
     if (key == 5) { g_phead = value; return AF_NET_OK; }                            // 5: MFMA policy head of the fp32 path (1/0)
     if (key == 4) { g_branch = value; return AF_NET_OK; }                           // 4: value branch on a side stream (fp32 path: 1/0; 2 forces it on path 5)
     if (key == 9) { g_fhead = value ? 1 : 0; return AF_NET_OK; }                    // 9: heads on the split-operand path (1/0)
-    if (key == 7) { g_f16s_abl = value; return AF_NET_OK; }                         // 7: A/B and profiling bits of af_conv_f16s.hip
+    if (key == 7) { g_f16s_abl = value; return AF_NET_OK; }                         // 7: A/B and profiling bits of af_conv_f16s.hip (F16sBits)
     return AF_NET_ERR_ARG;
 }
 

@@ -69,13 +69,15 @@ int af_net_forward(af_net* n, void* stream, const float* planes_dev, int32_t bat
  *          other board size, and bench.py's config2_fp32mfma leg)
  *   key 4: value branch on a side stream (default 1: on the fp32 path only; 2 forces it on path 5 too, for A/B)
  *   key 5: MFMA policy head of the fp32 path (default 1)
- *   key 7: bits of path 5 — 1 / 2 / 4 / 8 / 4096 profiling ablations (results wrong by design: no slab loads after the first position /
- *          no stores / loads from a hot address / stores, loads addressed modulo 128 positions), 16 VALU stem, 32 one workgroup per CU in
- *          the 32-channel-input layers; launch structures, each bit selecting the launch it replaced (same results bit for bit):
- *          64 two-halves launch on 15x15 (instead of the 4-tile / 3-tile classes + corner kernel), 128 one workgroup per position at
- *          batches <= 8 (instead of the pixel-tile split), 256 two launches per 32-wide block (instead of af_block_f16s),
- *          512 / 1024 the two-branch launch order at batches <= 8 / above (instead of the value branch as a workgroup class),
- *          2048 (r6) nine dependent launches at batches <= 8 (instead of the single launch of dataflow roles)
+ *   key 7: bits of path 5, named by enum F16sBits in csrc/af_conv_f16s.h; f16s_plan (af_conv_f16s.hip) is the one function that chooses launch variants from them.
+ *          kF16sProfilingBits 1 / 2 / 4 / 8 / 4096: profiling ablations (results wrong by design: no slab loads after the first position /
+ *          no stores / loads from a hot address / stores, loads addressed modulo 128 positions); kF16sValuStem 16: VALU stem;
+ *          kF16sOneWgPerCu 32: one workgroup per CU in the 32-channel-input layers.  Launch structures, each bit selecting the launch it
+ *          replaced (same results bit for bit): kF16sTwoHalves15 64 two-halves launch on 15x15 (instead of the 4-tile / 3-tile classes +
+ *          corner kernel), kF16sWgPerPosition 128 one workgroup per position at batches <= 8 (instead of the pixel-tile split),
+ *          kF16sTwoLaunchBlocks 256 two launches per 32-wide block (instead of af_block_f16s), kF16sBranchLaunchesSmall 512 /
+ *          kF16sBranchLaunchesBig 1024 the two-branch launch order at batches <= 8 / above (instead of the value branch as a workgroup
+ *          class), kF16sLaunchSequence 2048 (r6) nine dependent launches at batches <= 8 (instead of the single launch of dataflow roles)
  *   key 9: path 5 computes the heads itself — 1x1 head convolutions fused into the last conv of each branch, dense layers on
  *          the same split-operand MFMA (default 1); 0 = the fp32 head kernels of path 1 on fp32 planes
  * (removed in r6 with the kernels they selected: conv paths 0 / 2 / 3 / 4, keys 1 / 2 / 3 / 6 / 8) */

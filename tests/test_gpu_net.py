@@ -240,3 +240,33 @@ def test_forward_output_digests_are_pinned():
     import forward_digest
     assert forward_digest.digests() == {"S11_B600": "4f50b3f7d08132dc", "S11_B5": "441e8ce5d7f1f336",
                                         "S15_B300": "75d9f0dcac1b2d1d", "S15_B3": "57cc8bcb0af5cd8e"}
+
+
+def _forward_variants():
+    import sys
+    if GOLDEN not in sys.path:
+        sys.path.insert(0, GOLDEN)
+    import make_forward_variant_digests as m
+    return m
+
+
+@pytest.mark.parametrize("S,B", [(11, 1), (11, 8), (11, 9), (11, 300), (15, 3), (15, 127), (15, 128), (15, 300), (7, 5)])
+def test_forward_variants_match_the_recorded_digests(S, B):
+    """The host side of af_conv_f16s.hip chooses between launch forms (f16s_plan: single launch of roles / paired branches / branch
+    launches, tile split, half classes, fused blocks, ...) by batch size and the af_net_tune bits.  Policy and value of every setting
+    of tests/golden/make_forward_variant_digests.py — default, each key-7 A/B bit, the forced side stream, the fp32 heads, the fp32
+    path — at the smallest batches either side of every branch of that choice are the bytes recorded with the library of the commit
+    the record names (SHA-256, tests/golden/forward_variant_digests.json), and the key-7 values include/af_net.h documents as "same
+    results bit for bit" give the default's digest at the same shape."""
+    import json
+    m = _forward_variants()
+    assert (S, B) in m.SHAPES
+    with open(m.OUT) as f:
+        recorded = json.load(f)["digests"][m.shape_key(S, B)]
+    got = m.digests_of(S, B)
+    assert set(got) == set(recorded) == {m.setting_key(s) for s in m.SETTINGS}
+    for k in sorted(got):
+        print("%s %-12s %s" % (m.shape_key(S, B), k, "same" if got[k] == recorded[k] else "DIFFERENT: %s, recorded %s" % (got[k], recorded[k])))
+    assert got == recorded
+    for s in m.SAME_BITS_AS_DEFAULT:
+        assert got[m.setting_key(s)] == got["default"], (m.shape_key(S, B), m.setting_key(s))
