@@ -1293,18 +1293,24 @@ __global__ __launch_bounds__(256) void af_pack_copy(EngineParams P, int max_eps,
 // EXTERNAL mode, many games at once (arena: choose_best_player.py:38-60): set the roots / fetch the move results of n
 // games with one upload, one launch and one download instead of a device synchronisation and ~10 tiny copies per game
 // ----------------------------------------------------------------------------------------------
-// req[i] = { game, last_cell, random_a, reset_tree }, keys[i][2KW]
-__global__ __launch_bounds__(64) void af_set_roots_kernel(EngineParams P, int n, const int32_t* __restrict__ req, const u64* __restrict__ keys, int KW2) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    const int g = req[4 * i], last = req[4 * i + 1], ra = req[4 * i + 2], reset = req[4 * i + 3];
+// Player.get_action(state, last, random_a) for game g, by the wave that owns the request: `word` = key word `lane` of the new root
+// (read by the lanes below KW2 only).  The one place that knows the reset sequence; af_set_roots_kernel and af_match_step_kernel call it.
+__device__ __forceinline__ void install_root(const EngineParams& P, int g, int lane, int KW2, u64 word, int last, int ra, int reset) {
     if (reset) {                                                 // Player.reset(): player.py:48-51
         uint32_t* slots = P.hash + (size_t)g * (P.hash_mask + 1);
         for (uint32_t s_ = lane; s_ <= P.hash_mask; s_ += 64) slots[s_] = 0;
         if (lane == 0) { P.nodes[g] = 0; P.nfree[g] = 0; P.tau[g] = P.init_temp; P.episode[g] += 1; P.sel[g] = 0; P.plyctr[g] = 0; }
     }
-    if (lane < KW2) P.root[(size_t)g * KW2 + lane] = keys[(size_t)i * KW2 + lane];
+    if (lane < KW2) P.root[(size_t)g * KW2 + lane] = word;
     if (lane == 0) { P.root_last[g] = last; P.random_a[g] = ra ? 1 : 0; P.phase[g] = PH_MOVE_START; P.pending[g] = 0; P.status[g] = 0; }
+}
+
+// req[i] = { game, last_cell, random_a, reset_tree }, keys[i][2KW]
+__global__ __launch_bounds__(64) void af_set_roots_kernel(EngineParams P, int n, const int32_t* __restrict__ req, const u64* __restrict__ keys, int KW2) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const int g = req[4 * i], last = req[4 * i + 1], ra = req[4 * i + 2], reset = req[4 * i + 3];
+    install_root(P, g, lane, KW2, lane < KW2 ? keys[(size_t)i * KW2 + lane] : 0ull, last, ra, reset);
 }
 
 // out[i] = { action, has_policy, status/phase error (0 ok), tau bits lo, tau bits hi }, then policy[C] and visits[C]
@@ -1324,6 +1330,112 @@ __global__ __launch_bounds__(64) void af_move_results_kernel(EngineParams P, int
         o[8 + c] = __float_as_int(P.policy[(size_t)g * CP + c]);
         o[8 + C + c] = P.visits[(size_t)g * CP + c];
     }
+}
+
+// ----------------------------------------------------------------------------------------------
+// Device-resident arena (choose_best_player.py:38-63): game g is slot g of TWO EXTERNAL-mode engines, one per player; the mover of
+// ply k is player (g + k) % 2.  Both engines tick all the time (a tick returns at once for a game it has no move to search for);
+// af_match_step_kernel, launched after each tick + forward, is the hand-over: it takes a decided move out of the mover's engine,
+// plays it, tests for the end of the game, keeps the tally and installs the successor as the opponent engine's root.  No host in the loop.
+// ----------------------------------------------------------------------------------------------
+enum { MT_RUNNING = 0, MT_OVER = 1, MT_STOPPED = 2, MT_FAILED = 3, MT_UNUSED = 4 };    // MatchParams.ended
+enum { MC_DONE = 0, MC_PLIES = 1, MC_ERROR = 2, MC_N = 3 };                            // MatchParams.counters
+struct MatchParams {
+    int32_t* hdr;       // [0] games of the running match (<= G), [1] max_plies: device words, so that a captured step does not bake them in
+    int32_t *ply, *ended, *result, *error;   // [G]: plies played | MT_* | AF_MATCH_* | the engine's error code
+    int32_t* moves;     // [G][C] cells in the order played
+    u64* counters;      // MC_DONE games over, stopped or failed | MC_PLIES plies played | MC_ERROR first error code (0 = none)
+};
+
+__global__ __launch_bounds__(64) void af_match_start_kernel(EngineParams P0, EngineParams P1, MatchParams M, int n_games, int max_plies, int KW2) {
+    const int g = blockIdx.x, lane = threadIdx.x, C = P0.C;
+    if (g >= P0.G) return;
+    if (g == 0 && lane == 0) {
+        M.hdr[0] = n_games; M.hdr[1] = max_plies;
+        for (int i = 0; i < MC_N; ++i) M.counters[i] = 0ull;
+    }
+    for (int c = lane; c < C; c += 64) M.moves[(size_t)g * C + c] = -1;
+    if (lane == 0) {
+        M.ply[g] = 0; M.ended[g] = g < n_games ? MT_RUNNING : MT_UNUSED; M.result[g] = AF_MATCH_UNFINISHED; M.error[g] = 0;
+        // both players as created: nothing to search, and the noise streams (keyed by the episode counter, include/af_noise.h) at
+        // their beginning — a match is a function of the seeds, however many were played on these engines before
+        P0.phase[g] = PH_IDLE; P0.pending[g] = 0; P0.status[g] = 0; P0.episode[g] = 0;
+        P1.phase[g] = PH_IDLE; P1.pending[g] = 0; P1.status[g] = 0; P1.episode[g] = 0;
+    }
+    if (g < n_games) {                                          // player g % 2 moves first (choose_best_player.py:48), on the empty board
+        if (g & 1) install_root(P1, g, lane, KW2, 0ull, -1, 1, 1);
+        else install_root(P0, g, lane, KW2, 0ull, -1, 1, 1);
+    }
+}
+
+// P: the mover's engine (player p), Q: the opponent's
+template <int KW>
+__device__ __forceinline__ void match_step_game(const EngineParams& P, const EngineParams& Q, const MatchParams& M, int g, int lane, int p, int ply,
+                                                int max_plies) {
+    const int phase = rfli(P.phase[g]);
+    if (phase == PH_ERROR) {                                    // a failing game ends (and so cannot hang) the match
+        if (lane == 0) {
+            const int code = P.status[g];
+            M.error[g] = code; M.ended[g] = MT_FAILED;
+            atomicCAS(reinterpret_cast<unsigned long long*>(&M.counters[MC_ERROR]), 0ull, (unsigned long long)(long long)code);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&M.counters[MC_DONE]), 1ull);
+        }
+        return;
+    }
+    if (phase != PH_MOVE_DONE) return;
+    const int action = rfli(P.action[g]);
+    u64 rm[KW], rt[KW];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        rm[k] = rfl64(P.root[(size_t)g * 2 * KW + k]);
+        rt[k] = rfl64(P.root[(size_t)g * 2 * KW + KW + k]);
+    }
+    bool legal = action >= 0 && action < P.C && ply < P.C;
+    if (legal) legal = !bb_test<KW>(rm, action) && !bb_test<KW>(rt, action);
+    if (!legal) {                                               // (an engine never decides such a move: an assertion, not a path)
+        if (lane == 0) {
+            P.phase[g] = PH_IDLE; M.error[g] = AF_ERR_STATE; M.ended[g] = MT_FAILED;
+            atomicCAS(reinterpret_cast<unsigned long long*>(&M.counters[MC_ERROR]), 0ull, (unsigned long long)(long long)AF_ERR_STATE);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&M.counters[MC_DONE]), 1ull);
+        }
+        return;
+    }
+    // utils.py:275 step: the mover's stone becomes "theirs", the sides swap
+    u64 nm[KW], nt[KW];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { nm[k] = rt[k]; nt[k] = rm[k]; }
+    bb_set<KW>(nt, action);
+    float fv;
+    const int over = terminal_test<KW>(P, nm, nt, &fv);
+    const int nply = ply + 1;
+    if (lane == 0) {
+        M.moves[(size_t)g * P.C + ply] = action;
+        M.ply[g] = nply;
+        P.phase[g] = PH_IDLE;                                    // the move is consumed exactly once
+        atomicAdd(reinterpret_cast<unsigned long long*>(&M.counters[MC_PLIES]), 1ull);
+        if (over) {                                              // a non-draw is a win for the player who just moved (:62-63)
+            M.result[g] = fv == 0.0f ? AF_MATCH_DRAW : p;
+            M.ended[g] = MT_OVER;
+        } else if (nply >= max_plies) {
+            M.ended[g] = MT_STOPPED;
+        }
+        if (over || nply >= max_plies) atomicAdd(reinterpret_cast<unsigned long long*>(&M.counters[MC_DONE]), 1ull);
+    }
+    if (over || nply >= max_plies) return;
+    // the opponent's get_action(state, last_action = action, random_a = True); Player.reset() before its first move of the game
+    install_root(Q, g, lane, 2 * KW, key_word<KW>(nm, nt, lane), action, 1, nply < 2 ? 1 : 0);
+}
+
+template <int KW>
+__global__ __launch_bounds__(64) void af_match_step_kernel(EngineParams P0, EngineParams P1, MatchParams M) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= rfli(M.hdr[0])) return;
+    if (rfli(M.ended[g]) != MT_RUNNING) return;
+    const int max_plies = rfli(M.hdr[1]);
+    const int ply = rfli(M.ply[g]);
+    const int p = (g + ply) & 1;
+    if (p) match_step_game<KW>(P1, P0, M, g, lane, 1, ply, max_plies);
+    else match_step_game<KW>(P0, P1, M, g, lane, 0, ply, max_plies);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1385,6 +1497,16 @@ struct af_engine {
     bool memo = false;                // af_engine_memo_enable
     bool memo_budget_fixed = false;   // AF_MEMO_BUDGET given: af_engine_set_tick_budget leaves memo_budget alone
     size_t memo_entries = 0;
+};
+
+struct af_match {
+    af_engine *e0, *e1;
+    MatchParams M;
+    int device, G, C;
+    int32_t* block = nullptr;         // ply[G] | ended[G] | result[G] | error[G] | moves[G][C]: what af_match_results downloads
+    void* small = nullptr;            // hdr (2 x int32, padded to 16 bytes) | counters (MC_N x u64)
+    std::vector<int32_t> host;
+    bool started = false;
 };
 
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[af_engine] %s failed: %s\n", #x, hipGetErrorString(e_)); return AF_ERR_HIP; } } while (0)
@@ -1850,6 +1972,80 @@ int af_engine_stamp(af_engine* e, void* stream, int32_t slot) {
 int af_engine_stamps_async(af_engine* e, void* stream, uint64_t* out_pinned) {
     if (!e || !out_pinned || !e->stamps) return AF_ERR_ARG;
     HIP_OK(hipMemcpyAsync(out_pinned, e->stamps, AF_STAMP_SLOTS * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return AF_OK;
+}
+
+int af_match_create(af_engine* e0, af_engine* e1, af_match** out) {
+    if (!e0 || !e1 || !out || e0 == e1) return AF_ERR_ARG;
+    const EngineParams &A = e0->P, &B = e1->P;
+    if (A.mode != AF_MODE_EXTERNAL || B.mode != AF_MODE_EXTERNAL || e0->device != e1->device) return AF_ERR_ARG;
+    if (A.G != B.G || A.S != B.S || A.goal != B.goal) return AF_ERR_ARG;
+    HIP_OK(hipSetDevice(e0->device));
+    af_match* m = new af_match();
+    m->e0 = e0; m->e1 = e1; m->device = e0->device; m->G = A.G; m->C = A.C;
+    const size_t G = (size_t)A.G, ints = G * (4 + (size_t)A.C);
+    if (hipMalloc((void**)&m->block, ints * 4) != hipSuccess || hipMalloc(&m->small, 16 + MC_N * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        af_match_destroy(m);
+        return AF_ERR_HIP;
+    }
+    MatchParams& M = m->M;
+    M.ply = m->block; M.ended = m->block + G; M.result = m->block + 2 * G; M.error = m->block + 3 * G; M.moves = m->block + 4 * G;
+    M.hdr = (int32_t*)m->small; M.counters = (u64*)((char*)m->small + 16);
+    if (hipMemset(m->block, 0, ints * 4) != hipSuccess || hipMemset(m->small, 0, 16 + MC_N * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        af_match_destroy(m);
+        return AF_ERR_HIP;
+    }
+    m->host.resize(ints);
+    *out = m;
+    return AF_OK;
+}
+
+void af_match_destroy(af_match* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->block) (void)hipFree(m->block);
+    if (m->small) (void)hipFree(m->small);
+    delete m;
+}
+
+int af_match_start(af_match* m, void* stream, int32_t n_games, int32_t max_plies) {
+    if (!m || n_games < 1 || n_games > m->G || max_plies < 0 || max_plies > m->C) return AF_ERR_ARG;
+    if (max_plies == 0) max_plies = m->C;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(af_match_start_kernel, dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M, n_games, max_plies, 2 * m->e0->KW);
+    HIP_OK(hipGetLastError());
+    m->started = true;
+    return AF_OK;
+}
+
+int af_match_step(af_match* m, void* stream) {
+    if (!m || !m->started) return AF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (m->e0->KW == 2) hipLaunchKernelGGL((af_match_step_kernel<2>), dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M);
+    else hipLaunchKernelGGL((af_match_step_kernel<4>), dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M);
+    HIP_OK(hipGetLastError());
+    return AF_OK;
+}
+
+int af_match_progress_async(af_match* m, void* stream, uint64_t* out_pinned) {
+    if (!m || !out_pinned) return AF_ERR_ARG;
+    HIP_OK(hipMemcpyAsync(out_pinned, m->M.counters, MC_N * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return AF_OK;
+}
+
+int af_match_results(af_match* m, void* stream, int32_t* result, int32_t* lengths, int32_t* moves) {
+    if (!m || !m->started) return AF_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t G = (size_t)m->G, C = (size_t)m->C;
+    HIP_OK(hipMemcpyAsync(m->host.data(), m->block, m->host.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const int32_t* h = m->host.data();
+    if (lengths) memcpy(lengths, h, G * 4);
+    if (result) memcpy(result, h + 2 * G, G * 4);
+    if (moves) memcpy(moves, h + 4 * G, G * C * 4);
+    for (size_t g = 0; g < G; ++g) if (h[3 * G + g] < 0) return h[3 * G + g];
     return AF_OK;
 }
 

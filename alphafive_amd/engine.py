@@ -93,6 +93,13 @@ def lib():
         L.af_engine_memo_stats.argtypes = [vp, vp, u64p]
         L.af_engine_memo_epoch.argtypes = [vp]
         L.af_engine_memo_epoch.restype = C.c_int64
+        L.af_match_create.argtypes = [vp, vp, C.POINTER(vp)]
+        L.af_match_destroy.argtypes = [vp]
+        L.af_match_destroy.restype = None
+        L.af_match_start.argtypes = [vp, vp, C.c_int32, C.c_int32]
+        L.af_match_step.argtypes = [vp, vp]
+        L.af_match_progress_async.argtypes = [vp, vp, vp]
+        L.af_match_results.argtypes = [vp, vp, i32p, i32p, i32p]
         L.af_engine_tree_dump.argtypes = [vp, C.c_int32, C.c_int32, u64p, i32p, i32p, f32p, f32p, u8p]
         L.af_engine_load_tree.argtypes = [vp, C.c_int32, C.c_int32, u64p, i32p, i32p, f32p, f32p, u8p]
         L.af_state_to_key.argtypes = [C.c_char_p, C.c_int32, u64p]
@@ -371,6 +378,20 @@ def assemble_episode(raw, S, gamma):
     return rec, result
 
 
+def resolve_weights_version(pv, explicit=None):
+    """The weight-version source of evaluator `pv` (SelfPlayEngine._resolve_weights_version has the rules) -> (callable or None,
+    missing): missing = pv takes bind_outputs but names no version, so nothing that replays its launches may be built on it."""
+    if explicit is not None:
+        return (explicit if callable(explicit) else (lambda: explicit)), False
+    ver = getattr(pv, "weights_version", None)
+    if callable(ver):
+        return ver, False
+    owner = getattr(pv, "__self__", None)
+    if owner is not None and hasattr(owner, "version"):
+        return (lambda: owner.version), False
+    return None, hasattr(pv, "bind_outputs")
+
+
 class SelfPlayEngine:
     """G concurrent self-play games on one GPU: the device-resident replacement of
     main.py:50-55 (5 worker processes running Player.run) + NetworkAPI batching.
@@ -463,20 +484,12 @@ class SelfPlayEngine:
         belongs to (pv_device=net.eval_device).  An evaluator that takes bind_outputs (i.e. one of ours, whose Python wrapper
         is the only place that reloads weights) without any version source would replay stale weights silently: refused — by
         run_ticks_graph() and by eval_memo=, not by the constructor (eager tick() users are not affected)."""
-        if explicit is not None:
-            return explicit if callable(explicit) else (lambda: explicit)
-        pv = self.pv_device
-        ver = getattr(pv, "weights_version", None)
-        if callable(ver):
-            return ver
-        owner = getattr(pv, "__self__", None)
-        if owner is not None and hasattr(owner, "version"):
-            return lambda: owner.version
-        if hasattr(pv, "bind_outputs"):
+        ver, missing = resolve_weights_version(self.pv_device, explicit)
+        if missing:
             # one of ours without a version source: eager tick() is fine (the Python wrapper reloads), anything that replays
             # launches or reuses stored bits (run_ticks_graph, eval_memo) is refused where it is asked for
             self._weights_version_missing = True
-        return None
+        return ver
 
     def _graph_key(self, n):
         ver = self._weights_version

@@ -205,6 +205,42 @@ int af_engine_progress_async(af_engine* e, void* stream, uint64_t* out_pinned);
 int af_engine_stamp(af_engine* e, void* stream, int32_t slot);
 int af_engine_stamps_async(af_engine* e, void* stream, uint64_t* out_pinned);
 
+/* Device-resident checkpoint arena (choose_best_player.py:38-63) — an ADDITIVE extension of ABI v6: af_abi_version() still answers 6,
+ * a caller detects these entry points by symbol (dlsym / hasattr on af_match_create).
+ * A match couples two AF_MODE_EXTERNAL engines, one per player (weight set): game g is slot g of both, player g % 2 moves first and
+ * the mover of ply k is player (g + k) % 2, each searching on its OWN tree with get_action(state, last_action, random_a = True)
+ * (:52; Player.reset() before a player's first move of a game, :43-44).  The driver keeps both engines ticking and evaluating,
+ *     tick(e0), forward 0, af_match_step, tick(e1), forward 1, af_match_step, ...
+ * and af_match_step does on the device what the host loop did between two moves: for every game whose mover has decided
+ * (AF_STATUS_MOVE_DONE) it appends the cell to the game's move list, plays it, runs is_game_over (utils.py:199) on the successor,
+ * tallies a draw or a win of the player who just moved (:62-63), stops a game that has reached max_plies unfinished, and otherwise
+ * installs the successor as the root of the same slot in the opponent's engine (what af_engine_set_roots does).  A game whose
+ * engine reports an error ends with that code.  Nothing here synchronises except af_match_start (may) and af_match_results (does).
+ *   af_match_create   AF_ERR_ARG unless both engines are AF_MODE_EXTERNAL, on one device, with equal num_games, board_size and goal.
+ *                     Allocates all device memory of the match.  Destroy the match before its engines.
+ *   af_match_start    clears the match state, parks every slot of both engines (idle, noise streams at their beginning: a match is
+ *                     a function of the engines' seeds, whatever was played on them before) and gives game i < n_games its empty-
+ *                     board root in engine i % 2.  1 <= n_games <= num_games; 1 <= max_plies <= C (0 = C).
+ *   af_match_step     one launch, no synchronisation, no allocation: capturable.  n_games and max_plies live in device memory, so a
+ *                     captured step stays valid across af_match_start calls; the engines' by-value launch parameters are baked in
+ *                     as in af_engine_tick.
+ *   af_match_progress_async   24-byte copy, same contract as af_engine_progress_async: out[0] = games over, stopped or failed,
+ *                     out[1] = plies played, out[2] = first error code as int64 (0 = none).  The match is finished when out[0] == n_games.
+ *   af_match_results  one download (synchronises).  result[g] = AF_MATCH_WIN0 / WIN1 / DRAW / UNFINISHED, lengths[g] = plies played,
+ *                     moves[g][C] = cells in the order played, -1 beyond lengths[g]; any of them may be NULL.  Returns the first
+ *                     per-game error code if a game failed, else 0. */
+#define AF_MATCH_UNFINISHED (-1)
+#define AF_MATCH_WIN0 0
+#define AF_MATCH_WIN1 1
+#define AF_MATCH_DRAW 2
+typedef struct af_match af_match;
+int af_match_create(af_engine* e0, af_engine* e1, af_match** out);
+void af_match_destroy(af_match* m);
+int af_match_start(af_match* m, void* stream, int32_t n_games, int32_t max_plies);
+int af_match_step(af_match* m, void* stream);
+int af_match_progress_async(af_match* m, void* stream, uint64_t* out_pinned);
+int af_match_results(af_match* m, void* stream, int32_t* result, int32_t* lengths, int32_t* moves);
+
 /* tree inspection (tests / Player.tree): nodes of game g in storage order.
  * n has the "w is fp32-typed" flag stripped into f32[]. Returns node count or <0. */
 int af_engine_tree_dump(af_engine* e, int32_t game, int32_t cap, uint64_t* keys, int32_t* sum_n, int32_t* n,
