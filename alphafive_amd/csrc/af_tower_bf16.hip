@@ -984,11 +984,12 @@ static int g_engine = 3;    // 3 (default, r4): af_tower_conv3 for a block's fir
 extern "C" {
 
 int af_tower_tune(int32_t key, int32_t value) {
-    if (key == 0) { g_depth = value; return AF_TOWER_OK; }
-    if (key == 1) { g_grid = value; return AF_TOWER_OK; }
-    if (key == 2) { g_abl = value; return AF_TOWER_OK; }
+    // only the values include/af_tower_bf16.h documents; a rejected call leaves the setting as it was
+    if (key == 0) { if (value != 0 && value != 8 && value != 12 && value != 16) return AF_TOWER_ERR_ARG; g_depth = value; return AF_TOWER_OK; }
+    if (key == 1) { if (value < 0) return AF_TOWER_ERR_ARG; g_grid = value; return AF_TOWER_OK; }
+    if (key == 2) { if (value < 0 || value > 7) return AF_TOWER_ERR_ARG; g_abl = value; return AF_TOWER_OK; }
     if (key == 3) { if (value != 0 && value != 2 && value != 3) return AF_TOWER_ERR_ARG; g_engine = value; return AF_TOWER_OK; }
-    if (key == 4) { g_heads = value; return AF_TOWER_OK; }
+    if (key == 4) { if (value != 0 && value != 1) return AF_TOWER_ERR_ARG; g_heads = value; return AF_TOWER_OK; }
     return AF_TOWER_ERR_ARG;
 }
 

@@ -71,7 +71,9 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
  * "no LDS reads" is the build-time macro AF_TOWER_ABL_NOLDS since r3: a run-time test in the MFMA loop was not free), key 3 = convolution kernels
  * (3 = default: af_tower_conv3 — epilogue under the other tile pair's MFMAs — for a block's first convolution and af_tower_conv for its
  * second; 0 = af_tower_conv for both, bit-identical to 3; 2 = af_tower_conv3 for both), key 4 = the heads' 1x1 convolutions (1 MFMA kernel,
- * 0 VALU kernel). */
+ * 0 VALU kernel).  Anything else — an unknown key, a ring depth other than 0 / 8 / 12 / 16, a negative workgroup count, ablation
+ * bits outside 0..7, an engine other than 0 / 2 / 3, a heads kernel other than 0 / 1 — returns AF_TOWER_ERR_ARG and leaves the
+ * setting as it was. */
 int af_tower_tune(int32_t key, int32_t value);
 
 int64_t af_tower_flops_per_position(const af_tower* t);   /* 2*MAC of the tower, direct convolution */

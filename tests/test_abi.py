@@ -87,3 +87,24 @@ def test_net_libraries_export_every_declared_symbol(lib, header, libname, prefix
     fn = getattr(nl, prefix + "strerror")
     fn.restype = ctypes.c_char_p
     assert fn(-1) == b"bad argument"
+
+
+def test_tower_tune_accepts_only_documented_values(lib):
+    """af_tower_tune (include/af_tower_bf16.h): key 0 ring depth 0 / 8 / 12 / 16, key 1 workgroups >= 0, key 2 ablation bits 0..7,
+    key 3 engine 0 / 2 / 3, key 4 heads kernel 0 / 1; everything else is AF_TOWER_ERR_ARG (a depth of 5 used to mean 8 silently).
+    tests/test_gpu_tower_exact.py shows on the GPU that a rejected call leaves the previous setting in force."""
+    nl = ctypes.CDLL(os.path.join(REPO, "alphafive_amd", "_lib", "libaf_tower.so"))
+    tune = nl.af_tower_tune
+    tune.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    good = {0: (8, 12, 16, 0), 1: (1, 3, 1 << 20, 0), 2: (1, 7, 0), 3: (0, 2, 3), 4: (0, 1)}      # the default last
+    bad = {0: (-1, 1, 5, 7, 9, 24, 32), 1: (-1, -256), 2: (-1, 8, 255), 3: (-1, 1, 4), 4: (-1, 2), 5: (0,), -1: (0,)}
+    try:
+        for key, values in good.items():
+            for v in values:
+                assert tune(key, v) == 0, (key, v)
+        for key, values in bad.items():
+            for v in values:
+                assert tune(key, v) == -1, (key, v)
+    finally:
+        for key, values in good.items():
+            tune(key, values[-1])

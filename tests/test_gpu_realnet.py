@@ -393,6 +393,7 @@ def test_deep_bf16_tower_kernel_matches_fp32_reference(blocks):
     # weights on both sides; the kernel keeps fp32 between the layers where the torch path rounds to bf16
     net.vfc1 = (net.vfc1[0], (torch.randn(64, generator=g) * 0.1).to("cuda", torch.bfloat16))
     net.pfc = (net.pfc[0], (torch.randn(121, generator=g) * 0.1).to("cuda", torch.bfloat16))
+    net.vfc2 = (net.vfc2[0], (torch.randn(1, generator=g) * 0.1 + 0.25).to("cuda", torch.bfloat16))    # (drawn last: the other layers' draws stay as they were)
     pv = net.select_backend("hip", B)
     pd, vd = (t.clone() for t in pv(x))
     pt, vt = net.eval_hip_torch_dense(x)
