@@ -1438,9 +1438,6 @@ __global__ __launch_bounds__(64) void af_match_step_kernel(EngineParams P0, Engi
     else match_step_game<KW>(P0, P1, M, g, lane, 0, ply, max_plies);
 }
 
-// ----------------------------------------------------------------------------------------------
-// host side
-// ----------------------------------------------------------------------------------------------
 // Evaluation memo, the writing side: one wave per game, launched after the forward that evaluated this tick's parked leaves.  Reads
 // nothing the tick kernel writes concurrently (same stream, a launch of its own) and the tick kernel never writes the memo, so
 // neither side can see a torn entry.  Inside this launch an entry has one writer: the first wave whose atomicMax of the launch
@@ -1481,19 +1478,20 @@ __global__ __launch_bounds__(64) void af_memo_insert_kernel(EngineParams P, cons
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------------
 struct af_engine {
     EngineParams P;
     int device;
     int KW;
     std::vector<void*> allocs;
     std::vector<int32_t> h_i32, h_i32b;
-    int32_t* pack_dev = nullptr;      // staging buffer of af_engine_pop_episodes
-    char* stage_dev = nullptr;        // staging buffer of af_engine_set_roots / af_engine_move_results
+    char* stage_dev = nullptr;        // staging buffer of af_engine_set_roots / af_engine_move_results / af_engine_pop_episodes: stage_reserve
     size_t stage_cap = 0;
-    int64_t pack_cap = 0;
     std::vector<int32_t> pack_host;
     std::vector<u64> h_ct;
-    unsigned long long* stamps = nullptr;   // af_engine_stamp (allocated on first use; freed with the other allocations)
+    unsigned long long* stamps = nullptr;   // [AF_STAMP_SLOTS], af_engine_stamp
     bool memo = false;                // af_engine_memo_enable
     bool memo_budget_fixed = false;   // AF_MEMO_BUDGET given: af_engine_set_tick_budget leaves memo_budget alone
     size_t memo_entries = 0;
@@ -1525,6 +1523,63 @@ static int dalloc(af_engine* e, T** p, size_t n) {
     e->allocs.push_back(q);
     *p = (T*)q;
     return AF_OK;
+}
+
+// e->stage_dev holds at least `bytes`; grows to twice what was asked for, so that a slowly growing batch does not reallocate each time
+// (af_engine_pop_episodes bounds its request, so the buffer ends at 2 x 264 MB at the most).
+// Its users wait for their stream before they return, so the buffer is free whenever an entry point is entered.
+static int stage_reserve(af_engine* e, size_t bytes) {
+    if (e->stage_cap >= bytes) return AF_OK;
+    if (e->stage_dev) (void)hipFree(e->stage_dev);
+    e->stage_dev = nullptr; e->stage_cap = 0;
+    HIP_OK(hipMalloc((void**)&e->stage_dev, bytes * 2));
+    e->stage_cap = bytes * 2;
+    return AF_OK;
+}
+
+// a position: stones on the board only, no cell owned by both colours (key = KW words of one colour, then KW of the other)
+static bool valid_position(const EngineParams& P, int KW, const uint64_t* key) {
+    for (int k = 0; k < KW; ++k)
+        if (((key[k] | key[KW + k]) & ~P.boardmask[k]) || (key[k] & key[KW + k])) return false;
+    return true;
+}
+
+// The engine's KW (2 or 4 key words per colour) as the compile-time constant KW_ of the statement given; WITH_FLAG does the same for
+// a bool.  The order of the branches is the order in which the kernels are instantiated: leave it.
+#define WITH_KW(kw, ...) do { if ((kw) == 2) { constexpr int KW_ = 2; __VA_ARGS__; } else { constexpr int KW_ = 4; __VA_ARGS__; } } while (0)
+#define WITH_FLAG(flag, NAME, ...) do { if (flag) { constexpr bool NAME = true; __VA_ARGS__; } else { constexpr bool NAME = false; __VA_ARGS__; } } while (0)
+
+// The tree readers' view of one game: waits for the device, then bs = node_sum of the slots ever used (bs.size() = the store's high-water
+// mark) and *live = how many of them hold a node (a negative sum marks a slot the collector freed).
+static int live_nodes(af_engine* e, int game, std::vector<int32_t>& bs, int* live) {
+    const EngineParams& P = e->P;
+    HIP_OK(hipDeviceSynchronize());
+    int32_t hw;
+    HIP_OK(hipMemcpy(&hw, P.nodes + game, 4, hipMemcpyDeviceToHost));
+    bs.resize((size_t)(hw > 0 ? hw : 0));
+    if (hw > 0) HIP_OK(hipMemcpy(bs.data(), P.node_sum + (size_t)game * P.node_cap, (size_t)hw * 4, hipMemcpyDeviceToHost));
+    *live = 0;
+    for (int32_t v : bs) *live += v >= 0;
+    return AF_OK;
+}
+
+// Node rows are [slot][W] on the device (W = CP for the edge arrays: padded cells) and [count][C] in the ABI.  Out: the live slots only.
+template <typename D, typename S>
+static void rows_out(D* dst, const std::vector<S>& src, const std::vector<int32_t>& bs, int W, int C) {
+    size_t o = 0;
+    for (size_t i = 0; i < bs.size(); ++i) {
+        if (bs[i] < 0) continue;                     // slot freed by the collector
+        for (int c = 0; c < C; ++c) dst[o * C + c] = (D)src[i * W + c];
+        ++o;
+    }
+}
+// ... and in: `count` rows, the padding zeroed
+template <typename D, typename S>
+static std::vector<D> rows_in(const S* src, int count, int W, int C) {
+    std::vector<D> dst((size_t)count * W, D(0));
+    for (size_t i = 0; i < (size_t)count; ++i)
+        for (int c = 0; c < C; ++c) dst[i * W + c] = (D)src[i * C + c];
+    return dst;
 }
 
 extern "C" {
@@ -1599,6 +1654,7 @@ int af_engine_create(const af_config* cfg, int32_t num_games, int32_t device, in
         A(rec_last, R); A(rec_action, R);
     }
 #undef A
+    if (rc == AF_OK) rc = dalloc(e, &e->stamps, (size_t)AF_STAMP_SLOTS);
     if (rc != AF_OK) { af_engine_destroy(e); return rc; }
     // initial state
     std::vector<int32_t> ph(G, mode == AF_MODE_SELFPLAY ? PH_MOVE_START : PH_IDLE), rl(G, -1);
@@ -1615,7 +1671,6 @@ void af_engine_destroy(af_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     for (void* p : e->allocs) (void)hipFree(p);
-    if (e->pack_dev) (void)hipFree(e->pack_dev);
     if (e->stage_dev) (void)hipFree(e->stage_dev);
     delete e;
 }
@@ -1628,15 +1683,8 @@ int32_t af_engine_max_plies(const af_engine* e) { return e->P.max_ply; }
 int af_engine_tick(af_engine* e, void* stream, const float* policy_dev, const float* value_dev, float* planes_dev) {
     if (!e || !planes_dev) return AF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-#define AF_TICK(KW_, W_, M_) hipLaunchKernelGGL((af_tick_kernel<KW_, W_, M_>), dim3(e->P.G), dim3(64), 0, st, e->P, policy_dev, value_dev, planes_dev)
-    if (e->memo) {
-        if (e->KW == 2) { if (e->P.w64) AF_TICK(2, true, true); else AF_TICK(2, false, true); }
-        else { if (e->P.w64) AF_TICK(4, true, true); else AF_TICK(4, false, true); }
-    } else {
-        if (e->KW == 2) { if (e->P.w64) AF_TICK(2, true, false); else AF_TICK(2, false, false); }
-        else { if (e->P.w64) AF_TICK(4, true, false); else AF_TICK(4, false, false); }
-    }
-#undef AF_TICK
+    WITH_FLAG(e->memo, MEMO_, WITH_KW(e->KW, WITH_FLAG(e->P.w64, W64_,
+        hipLaunchKernelGGL((af_tick_kernel<KW_, W64_, MEMO_>), dim3(e->P.G), dim3(64), 0, st, e->P, policy_dev, value_dev, planes_dev))));
     HIP_OK(hipGetLastError());
     return AF_OK;
 }
@@ -1666,8 +1714,7 @@ int af_engine_memo_enable(af_engine* e, int32_t log2_buckets, int32_t max_stones
 int af_engine_memo_insert(af_engine* e, void* stream, const float* policy_dev, const float* value_dev) {
     if (!e || !e->memo || !policy_dev || !value_dev) return AF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (e->KW == 2) hipLaunchKernelGGL((af_memo_insert_kernel<2>), dim3(e->P.G), dim3(64), 0, st, e->P, policy_dev, value_dev);
-    else hipLaunchKernelGGL((af_memo_insert_kernel<4>), dim3(e->P.G), dim3(64), 0, st, e->P, policy_dev, value_dev);
+    WITH_KW(e->KW, hipLaunchKernelGGL((af_memo_insert_kernel<KW_>), dim3(e->P.G), dim3(64), 0, st, e->P, policy_dev, value_dev));
     HIP_OK(hipGetLastError());
     return AF_OK;
 }
@@ -1721,44 +1768,14 @@ int af_engine_set_simulations(af_engine* e, int32_t sims, int32_t upper) {
     return AF_OK;
 }
 
+// The per-game forms are the batched ones with n = 1 on the null stream.  They take no stream, so they wait for the whole device
+// first (the caller's ticks may be on any stream) and, like the batched forms, for their own work before they return.
 int af_engine_set_root(af_engine* e, int32_t game, const uint64_t* key, int32_t last_cell, int32_t random_a,
                        int32_t reset_tree) {
     if (!e || !key || game < 0 || game >= e->P.G || e->P.mode != AF_MODE_EXTERNAL) return AF_ERR_ARG;
-    EngineParams& P = e->P;
-    const int KW = e->KW;
-    for (int k = 0; k < KW; ++k) {                 // a position: stones on the board only, no cell owned by both colours
-        if ((key[k] | key[KW + k]) & ~P.boardmask[k]) return AF_ERR_ARG;
-        if (key[k] & key[KW + k]) return AF_ERR_ARG;
-    }
-    if (last_cell < -1 || last_cell >= P.C) return AF_ERR_ARG;
+    if (last_cell < -1 || last_cell >= e->P.C) return AF_ERR_ARG;
     HIP_OK(hipDeviceSynchronize());
-    if (reset_tree) {   // Player.reset(): player.py:48-51
-        const size_t hcap = (size_t)P.hash_mask + 1;
-        HIP_OK(hipMemset(P.hash + (size_t)game * hcap, 0, hcap * 4));
-        int32_t zero = 0;
-        HIP_OK(hipMemcpy(P.nodes + game, &zero, 4, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(P.nfree + game, &zero, 4, hipMemcpyHostToDevice));
-        double tau = P.init_temp;
-        HIP_OK(hipMemcpy(P.tau + game, &tau, 8, hipMemcpyHostToDevice));
-        uint32_t ep;
-        HIP_OK(hipMemcpy(&ep, P.episode + game, 4, hipMemcpyDeviceToHost));
-        ep += 1;
-        HIP_OK(hipMemcpy(P.episode + game, &ep, 4, hipMemcpyHostToDevice));
-        uint32_t z = 0;
-        HIP_OK(hipMemcpy(P.sel + game, &z, 4, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(P.plyctr + game, &z, 4, hipMemcpyHostToDevice));
-    }
-    HIP_OK(hipMemcpy(P.root + (size_t)game * 2 * KW, key, (size_t)2 * KW * 8, hipMemcpyHostToDevice));
-    int32_t v = last_cell;
-    HIP_OK(hipMemcpy(P.root_last + game, &v, 4, hipMemcpyHostToDevice));
-    v = random_a ? 1 : 0;
-    HIP_OK(hipMemcpy(P.random_a + game, &v, 4, hipMemcpyHostToDevice));
-    v = PH_MOVE_START;
-    HIP_OK(hipMemcpy(P.phase + game, &v, 4, hipMemcpyHostToDevice));
-    v = 0;
-    HIP_OK(hipMemcpy(P.pending + game, &v, 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(P.status + game, &v, 4, hipMemcpyHostToDevice));
-    return AF_OK;
+    return af_engine_set_roots(e, nullptr, 1, &game, key, &last_cell, &random_a, &reset_tree);
 }
 
 int af_engine_set_roots(af_engine* e, void* stream, int32_t n, const int32_t* games, const uint64_t* keys, const int32_t* last_cells,
@@ -1770,19 +1787,12 @@ int af_engine_set_roots(af_engine* e, void* stream, int32_t n, const int32_t* ga
     std::vector<int32_t> req((size_t)4 * n);
     for (int i = 0; i < n; ++i) {
         if (games[i] < 0 || games[i] >= P.G || last_cells[i] < -1 || last_cells[i] >= P.C) return AF_ERR_ARG;
-        const uint64_t* k = keys + (size_t)i * KW2;
-        for (int q = 0; q < KW; ++q)
-            if (((k[q] | k[KW + q]) & ~P.boardmask[q]) || (k[q] & k[KW + q])) return AF_ERR_ARG;
+        if (!valid_position(P, KW, keys + (size_t)i * KW2)) return AF_ERR_ARG;
         req[4 * i] = games[i]; req[4 * i + 1] = last_cells[i]; req[4 * i + 2] = random_a ? random_a[i] : 0; req[4 * i + 3] = reset_tree ? reset_tree[i] : 0;
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t rb = (size_t)4 * n * 4, kb = (size_t)n * KW2 * 8, need = rb + kb;
-    if (e->stage_cap < need) {
-        if (e->stage_dev) (void)hipFree(e->stage_dev);
-        e->stage_dev = nullptr; e->stage_cap = 0;
-        HIP_OK(hipMalloc((void**)&e->stage_dev, need * 2));
-        e->stage_cap = need * 2;
-    }
+    const size_t rb = (size_t)4 * n * 4, kb = (size_t)n * KW2 * 8;
+    if (int rc = stage_reserve(e, rb + kb)) return rc;
     HIP_OK(hipMemcpyAsync(e->stage_dev, req.data(), rb, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->stage_dev + rb, keys, kb, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(af_set_roots_kernel, dim3(n), dim3(64), 0, st, P, n, (const int32_t*)e->stage_dev, (const u64*)(e->stage_dev + rb), KW2);
@@ -1799,13 +1809,8 @@ int af_engine_move_results(af_engine* e, void* stream, int32_t n, const int32_t*
     for (int i = 0; i < n; ++i) if (games[i] < 0 || games[i] >= P.G) return AF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int C = P.C, R = 8 + 2 * C, CP = 64 * e->KW;
-    const size_t gb = (size_t)n * 4, ob = (size_t)n * R * 4, need = gb + ob;
-    if (e->stage_cap < need) {
-        if (e->stage_dev) (void)hipFree(e->stage_dev);
-        e->stage_dev = nullptr; e->stage_cap = 0;
-        HIP_OK(hipMalloc((void**)&e->stage_dev, need * 2));
-        e->stage_cap = need * 2;
-    }
+    const size_t gb = (size_t)n * 4, ob = (size_t)n * R * 4;
+    if (int rc = stage_reserve(e, gb + ob)) return rc;
     HIP_OK(hipMemcpyAsync(e->stage_dev, games, gb, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(af_move_results_kernel, dim3(n), dim3(64), 0, st, P, n, (const int32_t*)e->stage_dev, (int32_t*)(e->stage_dev + gb), CP);
     HIP_OK(hipGetLastError());
@@ -1827,19 +1832,11 @@ int af_engine_move_results(af_engine* e, void* stream, int32_t n, const int32_t*
 int af_engine_move_result(af_engine* e, int32_t game, int32_t* action_cell, int32_t* has_policy, float* policy,
                           int32_t* visits, double* tau) {
     if (!e || game < 0 || game >= e->P.G) return AF_ERR_ARG;
-    EngineParams& P = e->P;
-    const int CP = 64 * e->KW;
     HIP_OK(hipDeviceSynchronize());
-    int32_t ph;
-    HIP_OK(hipMemcpy(&ph, P.phase + game, 4, hipMemcpyDeviceToHost));
-    if (ph == PH_ERROR) { int32_t st; HIP_OK(hipMemcpy(&st, P.status + game, 4, hipMemcpyDeviceToHost)); return st; }
-    if (ph != PH_MOVE_DONE) return AF_ERR_STATE;
-    if (action_cell) HIP_OK(hipMemcpy(action_cell, P.action + game, 4, hipMemcpyDeviceToHost));
-    if (has_policy) HIP_OK(hipMemcpy(has_policy, P.has_policy + game, 4, hipMemcpyDeviceToHost));
-    if (policy) HIP_OK(hipMemcpy(policy, P.policy + (size_t)game * CP, (size_t)P.C * 4, hipMemcpyDeviceToHost));
-    if (visits) HIP_OK(hipMemcpy(visits, P.visits + (size_t)game * CP, (size_t)P.C * 4, hipMemcpyDeviceToHost));
-    if (tau) HIP_OK(hipMemcpy(tau, P.tau + game, 8, hipMemcpyDeviceToHost));
-    return AF_OK;
+    int32_t cell;                                    // the batched form wants the actions; here every output is optional
+    const int rc = af_engine_move_results(e, nullptr, 1, &game, &cell, has_policy, policy, visits, tau);
+    if (rc == AF_OK && action_cell) *action_cell = cell;
+    return rc;
 }
 
 int64_t af_engine_pack_ints(const af_engine* e, int32_t max_episodes, int32_t max_plies) {
@@ -1866,24 +1863,20 @@ int af_engine_pop_episodes(af_engine* e, void* stream, int32_t cap, int32_t* met
     EngineParams& P = e->P;
     hipStream_t st = (hipStream_t)stream;
     const int C = P.C, KW2 = 2 * e->KW, MP = P.max_ply, R = 2 * KW2 + 2 * C + 2;
-    const int max_plies = cap * MP > (1 << 18) ? (1 << 18) : cap * MP;           // bounds the staging buffer (<= 264 MB at 11x11)
-    const int64_t ints = af_engine_pack_ints(e, cap, max_plies);
-    if (e->pack_cap < ints) {
-        if (e->pack_dev) (void)hipFree(e->pack_dev);
-        e->pack_dev = nullptr; e->pack_cap = 0;
-        HIP_OK(hipMalloc((void**)&e->pack_dev, (size_t)ints * 4));
-        e->pack_cap = ints;
-    }
-    int rc = af_engine_pack_episodes(e, stream, cap, max_plies, e->pack_dev);
+    const int max_plies = cap * MP > (1 << 18) ? (1 << 18) : cap * MP;           // bounds what is staged (<= 264 MB at 11x11)
+    int rc = stage_reserve(e, (size_t)af_engine_pack_ints(e, cap, max_plies) * 4);
+    if (rc) return rc;
+    int32_t* pack_dev = (int32_t*)e->stage_dev;
+    rc = af_engine_pack_episodes(e, stream, cap, max_plies, pack_dev);
     if (rc) return rc;
     const size_t head = 4 + (size_t)cap * 5;
     e->pack_host.resize(head);
-    HIP_OK(hipMemcpyAsync(e->pack_host.data(), e->pack_dev, head * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(e->pack_host.data(), pack_dev, head * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     const int n = e->pack_host[0], np = e->pack_host[1];
     if (n <= 0) return 0;
     e->pack_host.resize(head + (size_t)np * R);
-    HIP_OK(hipMemcpyAsync(e->pack_host.data() + head, e->pack_dev + head, (size_t)np * R * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(e->pack_host.data() + head, pack_dev + head, (size_t)np * R * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     const int32_t* H = e->pack_host.data();
     for (int i = 0; i < n; ++i) {
@@ -1959,18 +1952,13 @@ __global__ void af_stamp_kernel(unsigned long long* stamps, int slot) {
 
 int af_engine_stamp(af_engine* e, void* stream, int32_t slot) {
     if (!e || slot < 0 || slot >= AF_STAMP_SLOTS) return AF_ERR_ARG;
-    if (!e->stamps) {
-        HIP_OK(hipSetDevice(e->device));
-        int rc = dalloc(e, &e->stamps, (size_t)AF_STAMP_SLOTS);
-        if (rc != AF_OK) return rc;
-    }
     hipLaunchKernelGGL(af_stamp_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, e->stamps, (int)slot);
     HIP_OK(hipGetLastError());
     return AF_OK;
 }
 
 int af_engine_stamps_async(af_engine* e, void* stream, uint64_t* out_pinned) {
-    if (!e || !out_pinned || !e->stamps) return AF_ERR_ARG;
+    if (!e || !out_pinned) return AF_ERR_ARG;
     HIP_OK(hipMemcpyAsync(out_pinned, e->stamps, AF_STAMP_SLOTS * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     return AF_OK;
 }
@@ -2023,8 +2011,7 @@ int af_match_start(af_match* m, void* stream, int32_t n_games, int32_t max_plies
 int af_match_step(af_match* m, void* stream) {
     if (!m || !m->started) return AF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (m->e0->KW == 2) hipLaunchKernelGGL((af_match_step_kernel<2>), dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M);
-    else hipLaunchKernelGGL((af_match_step_kernel<4>), dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M);
+    WITH_KW(m->e0->KW, hipLaunchKernelGGL((af_match_step_kernel<KW_>), dim3(m->G), dim3(64), 0, st, m->e0->P, m->e1->P, m->M));
     HIP_OK(hipGetLastError());
     return AF_OK;
 }
@@ -2054,40 +2041,33 @@ int af_engine_tree_dump(af_engine* e, int32_t game, int32_t cap, uint64_t* keys,
     if (!e || game < 0 || game >= e->P.G) return AF_ERR_ARG;
     EngineParams& P = e->P;
     const int KW2 = 2 * e->KW, CP = 64 * e->KW, C = P.C;
-    HIP_OK(hipDeviceSynchronize());
-    int32_t hw;
-    HIP_OK(hipMemcpy(&hw, P.nodes + game, 4, hipMemcpyDeviceToHost));
-    const size_t nb = (size_t)game * P.node_cap;
-    std::vector<int32_t> bs((size_t)(hw > 0 ? hw : 1));
-    if (hw > 0) HIP_OK(hipMemcpy(bs.data(), P.node_sum + nb, (size_t)hw * 4, hipMemcpyDeviceToHost));
-    int live = 0;
-    for (int i = 0; i < hw; ++i) live += bs[i] >= 0;
+    std::vector<int32_t> bs;
+    int live;
+    if (int rc = live_nodes(e, game, bs, &live)) return rc;
     if (cap < live || live == 0) return live;        // size query (or nothing to copy)
-    std::vector<int32_t> bn((size_t)hw * CP);
-    std::vector<float> bw((size_t)hw * CP), bp((size_t)hw * CP);
-    std::vector<uint64_t> bk((size_t)hw * KW2);
-    HIP_OK(hipMemcpy(bk.data(), P.node_key + nb * KW2, (size_t)hw * KW2 * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(bn.data(), P.edge_n + nb * CP, (size_t)hw * CP * 4, hipMemcpyDeviceToHost));
+    const size_t hw = bs.size(), nb = (size_t)game * P.node_cap;
+    std::vector<int32_t> bn(hw * CP);
+    std::vector<float> bp(hw * CP);
+    std::vector<uint64_t> bk(hw * KW2);
+    HIP_OK(hipMemcpy(bk.data(), P.node_key + nb * KW2, hw * KW2 * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(bn.data(), P.edge_n + nb * CP, hw * CP * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(bp.data(), P.edge_p + nb * CP, hw * CP * 4, hipMemcpyDeviceToHost));
     if (P.w64) {                                     // fp64 store: w is rounded here, af_engine_tree_w64 has the exact rows
-        std::vector<double> bd((size_t)hw * CP);
-        HIP_OK(hipMemcpy(bd.data(), P.edge_w64 + nb * CP, (size_t)hw * CP * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < bd.size(); ++i) bw[i] = (float)bd[i];
-    } else
-    HIP_OK(hipMemcpy(bw.data(), P.edge_w + nb * CP, (size_t)hw * CP * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(bp.data(), P.edge_p + nb * CP, (size_t)hw * CP * 4, hipMemcpyDeviceToHost));
-    int o = 0;
-    for (int i = 0; i < hw; ++i) {
-        if (bs[i] < 0) continue;                     // slot freed by the collector
-        for (int k = 0; k < KW2; ++k) keys[(size_t)o * KW2 + k] = bk[(size_t)i * KW2 + k];
-        sum_n[o] = bs[i];
-        for (int c = 0; c < C; ++c) {
-            const int32_t raw = bn[(size_t)i * CP + c];
-            n[(size_t)o * C + c] = raw & 0x7fffffff;
-            f32[(size_t)o * C + c] = raw < 0 ? 1 : 0;
-            w[(size_t)o * C + c] = bw[(size_t)i * CP + c];
-            p[(size_t)o * C + c] = bp[(size_t)i * CP + c];
-        }
-        ++o;
+        std::vector<double> bd(hw * CP);
+        HIP_OK(hipMemcpy(bd.data(), P.edge_w64 + nb * CP, hw * CP * 8, hipMemcpyDeviceToHost));
+        rows_out(w, bd, bs, CP, C);
+    } else {
+        std::vector<float> bw(hw * CP);
+        HIP_OK(hipMemcpy(bw.data(), P.edge_w + nb * CP, hw * CP * 4, hipMemcpyDeviceToHost));
+        rows_out(w, bw, bs, CP, C);
+    }
+    rows_out(keys, bk, bs, KW2, KW2);                // (keys and sums are not padded: W = C)
+    rows_out(sum_n, bs, bs, 1, 1);
+    rows_out(p, bp, bs, CP, C);
+    rows_out(n, bn, bs, CP, C);
+    for (size_t i = 0; i < (size_t)live * C; ++i) {  // edge_n's sign bit is the "W is fp32-typed" flag
+        f32[i] = n[i] < 0 ? 1 : 0;
+        n[i] &= 0x7fffffff;
     }
     return live;
 }
@@ -2104,13 +2084,12 @@ int af_engine_load_tree(af_engine* e, int32_t game, int32_t count, const uint64_
     const size_t hcap = (size_t)P.hash_mask + 1, nb = (size_t)game * P.node_cap;
     std::vector<uint32_t> slots(hcap, 0u);
     std::vector<int32_t> bn((size_t)count * CP, 0);
-    std::vector<float> bw((size_t)count * CP, 0.0f), bp((size_t)count * CP, 0.0f);
     for (int i = 0; i < count; ++i) {
         const uint64_t* k = keys + (size_t)i * KW2;
-        for (int q = 0; q < KW; ++q)
-            if (((k[q] | k[KW + q]) & ~P.boardmask[q]) || (k[q] & k[KW + q])) return AF_ERR_ARG;
+        if (!valid_position(P, KW, k)) return AF_ERR_ARG;
         const u64* kk = reinterpret_cast<const u64*>(k);
-        uint32_t h = KW == 2 ? key_hash<2>(kk, kk + KW) : key_hash<4>(kk, kk + KW);
+        uint32_t h;
+        WITH_KW(KW, h = key_hash<KW_>(kk, kk + KW));
         for (;;) {
             h &= P.hash_mask;
             if (slots[h] == 0u) { slots[h] = (uint32_t)i + 1u; break; }
@@ -2122,10 +2101,9 @@ int af_engine_load_tree(af_engine* e, int32_t game, int32_t count, const uint64_
             const int32_t nn = n[(size_t)i * C + c];
             if (nn < 0) return AF_ERR_ARG;
             bn[(size_t)i * CP + c] = nn | (f32[(size_t)i * C + c] ? (int32_t)0x80000000 : 0);
-            bw[(size_t)i * CP + c] = w[(size_t)i * C + c];
-            bp[(size_t)i * CP + c] = p[(size_t)i * C + c];
         }
     }
+    const std::vector<float> bp = rows_in<float>(p, count, CP, C);
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(P.hash + (size_t)game * hcap, slots.data(), hcap * 4, hipMemcpyHostToDevice));
     if (count > 0) {
@@ -2133,10 +2111,12 @@ int af_engine_load_tree(af_engine* e, int32_t game, int32_t count, const uint64_
         HIP_OK(hipMemcpy(P.node_sum + nb, sum_n, (size_t)count * 4, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(P.edge_n + nb * CP, bn.data(), bn.size() * 4, hipMemcpyHostToDevice));
         if (P.w64) {
-            std::vector<double> bd(bw.begin(), bw.end());
+            const std::vector<double> bd = rows_in<double>(w, count, CP, C);
             HIP_OK(hipMemcpy(P.edge_w64 + nb * CP, bd.data(), bd.size() * 8, hipMemcpyHostToDevice));
-        } else
-        HIP_OK(hipMemcpy(P.edge_w + nb * CP, bw.data(), bw.size() * 4, hipMemcpyHostToDevice));
+        } else {
+            const std::vector<float> bw = rows_in<float>(w, count, CP, C);
+            HIP_OK(hipMemcpy(P.edge_w + nb * CP, bw.data(), bw.size() * 4, hipMemcpyHostToDevice));
+        }
         HIP_OK(hipMemcpy(P.edge_p + nb * CP, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
         HIP_OK(hipMemset(P.edge_c + nb * CP, 0, (size_t)count * CP * 4));
     }
@@ -2170,24 +2150,14 @@ int af_state_to_key(const char* state, int32_t S, uint64_t* key) {
 int af_engine_tree_w64(af_engine* e, int32_t game, int32_t cap, double* w) {
     if (!e || game < 0 || game >= e->P.G || !e->P.w64) return AF_ERR_ARG;
     EngineParams& P = e->P;
-    const int CP = 64 * e->KW, C = P.C;
-    HIP_OK(hipDeviceSynchronize());
-    int32_t hw;
-    HIP_OK(hipMemcpy(&hw, P.nodes + game, 4, hipMemcpyDeviceToHost));
-    const size_t nb = (size_t)game * P.node_cap;
-    std::vector<int32_t> bs((size_t)(hw > 0 ? hw : 1));
-    if (hw > 0) HIP_OK(hipMemcpy(bs.data(), P.node_sum + nb, (size_t)hw * 4, hipMemcpyDeviceToHost));
-    int live = 0;
-    for (int i = 0; i < hw; ++i) live += bs[i] >= 0;
+    const int CP = 64 * e->KW;
+    std::vector<int32_t> bs;
+    int live;
+    if (int rc = live_nodes(e, game, bs, &live)) return rc;
     if (cap < live || live == 0 || !w) return live;
-    std::vector<double> bd((size_t)hw * CP);
-    HIP_OK(hipMemcpy(bd.data(), P.edge_w64 + nb * CP, (size_t)hw * CP * 8, hipMemcpyDeviceToHost));
-    int o = 0;
-    for (int i = 0; i < hw; ++i) {
-        if (bs[i] < 0) continue;
-        for (int c = 0; c < C; ++c) w[(size_t)o * C + c] = bd[(size_t)i * CP + c];
-        ++o;
-    }
+    std::vector<double> bd(bs.size() * CP);
+    HIP_OK(hipMemcpy(bd.data(), P.edge_w64 + (size_t)game * P.node_cap * CP, bd.size() * 8, hipMemcpyDeviceToHost));
+    rows_out(w, bd, bs, CP, P.C);
     return live;
 }
 
@@ -2202,9 +2172,7 @@ int af_engine_set_tree_w64(af_engine* e, int32_t game, int32_t count, const doub
     HIP_OK(hipMemcpy(&hw, P.nodes + game, 4, hipMemcpyDeviceToHost));
     if (hw != count) return AF_ERR_STATE;
     if (count == 0) return AF_OK;
-    std::vector<double> bd((size_t)count * CP, 0.0);
-    for (int i = 0; i < count; ++i)
-        for (int c = 0; c < C; ++c) bd[(size_t)i * CP + c] = w[(size_t)i * C + c];
+    const std::vector<double> bd = rows_in<double>(w, count, CP, C);
     HIP_OK(hipMemcpy(P.edge_w64 + (size_t)game * P.node_cap * CP, bd.data(), bd.size() * 8, hipMemcpyHostToDevice));
     return AF_OK;
 }

@@ -521,7 +521,6 @@ class SelfPlayEngine:
                 if self._stamp_host is None:
                     self._stamp_host = torch.zeros(STAMP_SLOTS, dtype=torch.int64, pin_memory=True)
                     self._stamp_event = torch.cuda.Event()
-                    self.engine.stamp(0, torch.cuda.current_stream(self.dev).cuda_stream)     # (allocates the stamp array: not inside a capture)
                 torch.cuda.synchronize(self.dev)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):

@@ -121,8 +121,10 @@ int af_engine_set_training(af_engine* e, int32_t training);
 int af_engine_set_simulations(af_engine* e, int32_t simulation_per_step, int32_t upper_simulation_per_step);
 
 /* The same for n games at once (batched arena, choose_best_player.py:38-60): one upload + one launch / one launch + one
- * download on `stream` instead of a device synchronisation and ~10 small copies per game.  keys [n][2KW]; random_a and
- * reset_tree may be NULL (= 0); policies / visits [n][C], has_policy, taus may be NULL. */
+ * download on `stream`, which they wait for before they return.  The per-game forms above are these with n = 1 on the null
+ * stream, behind a device synchronisation (they take no stream, so they order themselves after the work on every stream);
+ * there every output pointer may be NULL.  keys [n][2KW]; random_a and reset_tree may be NULL (= 0); policies / visits
+ * [n][C], has_policy, taus may be NULL. */
 int af_engine_set_roots(af_engine* e, void* stream, int32_t n, const int32_t* games, const uint64_t* keys, const int32_t* last_cells,
                         const int32_t* random_a, const int32_t* reset_tree);
 int af_engine_move_results(af_engine* e, void* stream, int32_t n, const int32_t* games, int32_t* action_cells, int32_t* has_policy,

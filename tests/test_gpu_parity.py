@@ -398,6 +398,49 @@ def test_unpopped_episodes_apply_back_pressure_and_small_caps_keep_order():
     sp.close()
 
 
+def test_pop_episodes_into_padded_host_arrays_equals_the_packed_hand_off():
+    """af_engine_pop_episodes (padded host arrays, a staging buffer of its own) vs af_engine_pack_episodes (pop_raw) on two
+    engines that ran the same games: a prefix in (game, sequence) order under a small cap, then the rest."""
+    import ctypes as C
+    import torch
+    from alphafive_amd import engine as eng
+    from alphafive_amd.engine import SelfPlayEngine
+    S, G = 6, 4
+    cfg = make_cfg(board_size=S, goal=4, simulation_per_step=20, upper_simulation_per_step=30)
+    sps = [SelfPlayEngine(cfg, G, lambda x: pseudonet.pseudonet_torch(x, 4321, 8192), device=0, seed=99) for _ in range(2)]
+    for sp in sps:
+        sp.run_ticks(2400)                       # two episodes are <= 2 x 36 plies x 20 sims; then every game waits
+        sp.check()
+        assert sp.counters()["episodes"] == 2 * G
+    a, b = sps
+    MP, KW2, CC = b.engine.max_plies, b.engine.KW2, S * S
+    stream = torch.cuda.current_stream(b.dev).cuda_stream
+    seen = []
+    for cap, n_want in ((3, 3), (8, 2 * G - 3)):
+        want = a.pop_raw(cap)
+        meta, final = np.full((cap, 4), -7, np.int32), np.zeros(cap, np.float32)
+        keys = np.zeros((cap, MP, KW2), np.uint64)
+        pols, vis = np.zeros((cap, MP, CC), np.float32), np.zeros((cap, MP, CC), np.int32)
+        lasts, acts = np.zeros((cap, MP), np.int32), np.zeros((cap, MP), np.int32)
+        n = eng.lib().af_engine_pop_episodes(b.engine._h, stream, cap, eng._p(meta, C.c_int32), eng._p(final, C.c_float),
+                                             eng._p(keys, C.c_uint64), eng._p(pols, C.c_float), eng._p(vis, C.c_int32),
+                                             eng._p(lasts, C.c_int32), eng._p(acts, C.c_int32))
+        assert n == n_want == len(want)
+        for i, r in enumerate(want):
+            T = r["T"]
+            assert (int(meta[i, 0]), int(meta[i, 1]), int(meta[i, 2])) == (r["game"], r["seq"], T)
+            assert final[i:i + 1].view(np.uint32)[0] == np.array([r["final_value"]], np.float32).view(np.uint32)[0]
+            np.testing.assert_array_equal(keys[i, :T], r["keys"])
+            np.testing.assert_array_equal(pols[i, :T].view(np.uint32), r["policies"].view(np.uint32))
+            np.testing.assert_array_equal(vis[i, :T], r["visits"])
+            np.testing.assert_array_equal(lasts[i, :T], r["lasts"])
+            np.testing.assert_array_equal(acts[i, :T], r["actions"])
+            seen.append((r["game"], r["seq"]))
+    assert seen == [(g, q) for g in range(G) for q in range(2)]
+    for sp in sps:
+        sp.close()
+
+
 def test_engine_rejects_bad_configuration_and_roots():
     from alphafive_amd import engine as eng
     with pytest.raises(eng.EngineError):         # numpy's shape >= 1 gamma branch is not implemented: refuse, do not mis-sample
@@ -419,8 +462,43 @@ def test_engine_rejects_bad_configuration_and_roots():
     e.close()
 
 
+def test_per_game_calls_reject_bad_arguments_with_their_codes():
+    """af_engine_set_root / af_engine_move_result: the error code of each refusal, and a result read with no output wanted."""
+    import torch
+    from alphafive_amd import engine as eng
+    S = 6
+    cfg = make_cfg(board_size=S, goal=4, simulation_per_step=20, upper_simulation_per_step=30)
+    key = eng.state_to_key("g/g/g/g/g/g/", S)
+    e = eng.Engine(cfg, 1, mode=eng.MODE_EXTERNAL)
+    for game, last_cell in ((0, S * S), (0, -2), (1, -1)):
+        with pytest.raises(eng.EngineError, match=r"\(code -1\)"):        # AF_ERR_ARG
+            e.set_root(game, key, last_cell)
+    sp = eng.Engine(cfg, 1, mode=eng.MODE_SELFPLAY)
+    with pytest.raises(eng.EngineError, match=r"\(code -1\)"):
+        sp.set_root(0, key)
+    sp.close()
+    with pytest.raises(eng.EngineError, match=r"\(code -6\)"):            # AF_ERR_STATE: no root was ever set
+        e.move_result(0)
+    e.set_root(0, key, reset_tree=True)
+    planes = torch.zeros((1, 3, S, S), device="cuda")
+    pol, val = torch.zeros((1, S * S), device="cuda"), torch.zeros((1,), device="cuda")
+    for _ in range(200):
+        e.tick(pol.data_ptr(), val.data_ptr(), planes.data_ptr())
+        if e.status()[0] == eng.STATUS_MOVE_DONE:
+            break
+        pr, va = pseudonet.pseudonet_torch(planes, 7, 2048)
+        pol.copy_(pr.reshape(1, -1))
+        val.copy_(va.reshape(1))
+    assert e.status()[0] == eng.STATUS_MOVE_DONE
+    assert eng.lib().af_engine_move_result(e._h, 0, None, None, None, None, None) == 0      # every output is optional
+    cell, _, vis, _ = e.move_result(0)
+    assert 0 <= cell < S * S and vis.sum() > 0
+    e.close()
+
+
 def test_batched_roots_and_results_equal_the_per_game_calls():
-    """af_engine_set_roots / af_engine_move_results (one launch for n games) vs af_engine_set_root / af_engine_move_result."""
+    """af_engine_set_roots / af_engine_move_results (n games at once) and af_engine_set_root / af_engine_move_result (one game): both
+    forms against the C oracle's Player, bit for bit, and against each other."""
     import torch
     from alphafive_amd import engine as eng
     S, G = 6, 6
@@ -434,6 +512,17 @@ def test_batched_roots_and_results_equal_the_per_game_calls():
     games = [0, 2, 5]
     keys = np.stack([eng.state_to_key(utils.board_to_state(b_), S) for b_ in boards])
     lcs = [-1, 1 * S + 2, 3 * S + 1]
+    # the reference of both forms: one oracle Player per game, asked twice for the same position (the second search runs on the
+    # tree of the first).  reset() first: round 0 installs with reset_tree, which advances the episode counter.
+    want = [[], []]
+    for g, b_, last, ra in zip(games, boards, (None, (1, 2), (3, 1)), (False, True, False)):
+        orc = oracle.OraclePlayer(cfg, training=True, rng_mode=oracle.RNG_PHILOX, seed=9, game_id=g,
+                                  pseudo_salt=7, pseudo_peak=2048)
+        orc.reset()
+        for rnd in range(2):
+            opol, oact, ovis = orc.get_action(utils.board_to_state(b_), last, ra)
+            want[rnd].append((oact[0] * S + oact[1], opol, ovis, orc.tau))
+        orc.close()
     outs = []
     for batched in (False, True):
         e = eng.Engine(cfg, G, mode=eng.MODE_EXTERNAL, training=True, seed=9)
@@ -469,6 +558,13 @@ def test_batched_roots_and_results_equal_the_per_game_calls():
         with pytest.raises(eng.EngineError):
             e.set_roots(games, bad, lcs)
         e.close()
+    for arm in (outs[:2], outs[2:]):
+        for got_rnd, want_rnd in zip(arm, want):
+            for (cell, hp, po, vi, tau), (ocell, opol, ovis, otau) in zip(got_rnd, want_rnd):
+                assert cell == ocell and bool(hp) == (opol is not None) and tau == otau
+                if opol is not None:
+                    np.testing.assert_array_equal(po.view(np.uint32), opol.reshape(-1).view(np.uint32))
+                np.testing.assert_array_equal(vi, ovis)
     for a_, b_ in zip(outs[:2], outs[2:]):
         for x, y in zip(a_, b_):
             assert x[0] == y[0] and x[1] == y[1] and x[4] == y[4]
