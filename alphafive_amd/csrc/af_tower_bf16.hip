@@ -760,7 +760,7 @@ struct DenseArgs {
     const float* pb;      // [128] policy bias (padded with -inf-like for the 7 dead outputs)
     const float* vb1;     // [64]
     const float* vw2;     // [64]
-    float vb2;
+    const float* vb2;     // [1]: a device word, not a by-value argument — a replayed graph must see the value an update wrote
     float* policy;        // fp32 [B][121]
     float* value;         // fp32 [B]
     int batch;
@@ -905,11 +905,162 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
         s_red[wv][kg][nn] = part;
         __syncthreads();
         if (wv == 0 && kg == 0 && p0 + nn < A.batch) {
-            const float z = s_red[0][0][nn] + s_red[0][1][nn] + s_red[1][0][nn] + s_red[1][1][nn] + A.vb2;
+            const float z = s_red[0][0][nn] + s_red[0][1][nn] + s_red[1][0][nn] + s_red[1][1][nn] + A.vb2[0];
             A.value[pos] = tanhf(0.5f * z);
         }
         __syncthreads();
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Device weight packers (af_tower_update_device): fp32 weights in device memory (the layouts the host setters take: OIHW
+// convolutions, [in][out] dense layers) -> every weight-derived buffer of the handle, in place.  They restate, per output
+// element, what the host loops behind af_tower_set_block / _set_stem / _set_heads / _set_dense compute (those loops stay as
+// they are: tests/test_gpu_tower_update.py compares the two byte for byte).  A thread owns one 16-byte fragment row (8 bf16,
+// one vector store) or one fp32 word; the thread index is decoded by div / mod with compile-time region sizes, so every source
+// and destination index is in range by construction for the element counts af_tower_update_device has validated.  No scales,
+// no reductions: nothing here has to come back to the host, which is why the update is launches only.
+//
+// pack_bf16: the host bf16_rne in the same integer arithmetic (round to nearest even on the bit pattern: ties both ways, carry
+// into the exponent up to inf, denormals and -0 as they are; NaN keeps its sign and gets a quiet bit).  Not a conversion
+// instruction: the bytes must be the host packer's on every class of input.
+__device__ __forceinline__ uint32_t pack_bf16(float f) {
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return ((u >> 16) | 0x40u) & 0xffffu;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+__device__ __forceinline__ float pack_bf16_f32(float f) { return __uint_as_float(pack_bf16(f) << 16); }
+__device__ __forceinline__ int pack_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }   // MFMA row -> output (pack_tower)
+__device__ __forceinline__ uint4 pack_row(const uint32_t (&h)[8]) {
+    return uint4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+}
+
+constexpr int kPackBlocks = 8;                                          // residual blocks per launch (their pointers are kernel arguments)
+constexpr int kRowsW1 = 4 * 72 * 64, kRowsW2 = 4 * 80 * 64;             // fragment rows of a block's two convolutions
+constexpr int kPackBlockThreads = kRowsW1 + kRowsW2 + 128 + 128;        // + b1 + b2 words: 39,168 = 153 x 256
+struct PackBlocksArgs {
+    const float* src[kPackBlocks][6];    // c1_w, c1_b, c2_w, c2_b, res_w, res_b
+    uint4* w1[kPackBlocks];
+    uint4* w2[kPackBlocks];
+    float* b1[kPackBlocks];
+    float* b2[kPackBlocks];
+};
+
+// grid (153, blocks of this launch): blockIdx.y picks the residual block
+__global__ __launch_bounds__(256) void af_tower_pack_blocks_kernel(PackBlocksArgs A) {
+    const int b = blockIdx.y;
+    int r = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (r < kRowsW1 + kRowsW2) {
+        const bool second = r >= kRowsW1;
+        const int q = second ? r - kRowsW1 : r, NS = second ? 80 : 72;            // q < 4 * NS * 64
+        const int lane = q & 63, s = (q >> 6) % NS, wv = (q >> 6) / NS;           // wv < 4
+        const int co = 32 * wv + pack_perm(lane & 31);                            // < 128
+        const int cc = s < 72 ? s % 8 : s - 72;                                   // < 8
+        const int ci = 16 * cc + 8 * (lane >> 5);                                 // ci + 7 < 128
+        uint32_t h[8];
+        if (s < 72) {
+            const float* p = A.src[b][second ? 2 : 0] + ((size_t)co * 128 + ci) * 9 + s / 8;      // tap s / 8 < 9
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(p[9 * e]);
+        } else {
+            const float* p = A.src[b][4] + (size_t)co * 128 + ci;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(p[e]);
+        }
+        (second ? A.w2[b] : A.w1[b])[q] = pack_row(h);
+        return;
+    }
+    r -= kRowsW1 + kRowsW2;
+    if (r < 128) { A.b1[b][r] = A.src[b][1][r]; return; }
+    r -= 128;
+    if (r < 128) A.b2[b][r] = A.src[b][3][r] + A.src[b][5][r];
+}
+
+// stem, the heads' 1x1 convolutions and the dense layers: one launch, the thread index walks the regions below in order
+constexpr int kRowsStem = 4 * 8 * 64, kRowsHeadsA = 8 * 64, kRowsWp = 121 * 4 * 64, kRowsWv = 31 * 2 * 64;
+constexpr int kPackEndsThreads = kRowsStem + 128 + 20 * 128 + 20 + kRowsHeadsA + 32 + kRowsWp + kRowsWv + 121 + 64 + 64 + 1;
+struct PackEndsArgs {
+    const float *stem_w, *stem_b, *vconv_w, *vconv_b, *pconv_w, *pconv_b, *vfc1_w, *vfc1_b, *vfc2_w, *vfc2_b, *pfc_w, *pfc_b;
+    uint4* o_stem_w;
+    float* o_stem_b;
+    float *o_heads_w, *o_heads_b;
+    uint4* o_heads_a;
+    float* o_heads_b32;
+    uint4 *o_dense_wp, *o_dense_wv;
+    float *o_dense_pb, *o_dense_vb1, *o_dense_vw2, *o_dense_vb2;
+};
+
+__global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A) {
+    int r = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (r < kRowsStem) {                         // [wave][k-step][lane]: group g = 2 s + (lane >> 5) = (cin, ky), 5 taps + 3 zeros; g = 15 is zero
+        const int lane = r & 63, s = (r >> 6) & 7, wv = r >> 9;                   // wv < 4
+        const int co = 32 * wv + pack_perm(lane & 31), g = 2 * s + (lane >> 5);
+        uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (g < 15) {
+            const float* p = A.stem_w + (((size_t)co * 3 + g / 5) * 5 + g % 5) * 5;
+#pragma unroll
+            for (int e = 0; e < 5; ++e) h[e] = pack_bf16(p[e]);
+        }
+        A.o_stem_w[r] = pack_row(h);
+        return;
+    }
+    r -= kRowsStem;
+    if (r < 128) { A.o_stem_b[r] = A.stem_b[r]; return; }
+    r -= 128;
+    if (r < 20 * 128) {                          // heads_w [20][128]: rows 0-3 value conv, 4-19 policy conv, bf16 values held in fp32
+        const int c = r >> 7, k = r & 127;
+        A.o_heads_w[r] = pack_bf16_f32(c < 4 ? A.vconv_w[c * 128 + k] : A.pconv_w[(c - 4) * 128 + k]);
+        return;
+    }
+    r -= 20 * 128;
+    if (r < 20) { A.o_heads_b[r] = r < 4 ? A.vconv_b[r] : A.pconv_b[r - 4]; return; }
+    r -= 20;
+    if (r < kRowsHeadsA) {                       // [k-step][lane]: output o = perm(lane & 31) (zero rows for o >= 20), channels 16 step + 8 (lane >> 5) + e
+        const int lane = r & 63, step = r >> 6;                                   // step < 8
+        const int o = pack_perm(lane & 31), ch = 16 * step + 8 * (lane >> 5);     // ch + 7 < 128
+        uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (o < 20) {
+            const float* p = (o < 4 ? A.vconv_w + o * 128 : A.pconv_w + (o - 4) * 128) + ch;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(p[e]);
+        }
+        A.o_heads_a[r] = pack_row(h);
+        return;
+    }
+    r -= kRowsHeadsA;
+    if (r < 32) { A.o_heads_b32[r] = r < 4 ? A.vconv_b[r] : (r < 20 ? A.pconv_b[r - 4] : 0.0f); return; }
+    r -= 32;
+    if (r < kRowsWp) {                           // [k-step][out tile][lane]: pfc [1936][121], outputs 121..127 are zero rows
+        const int lane = r & 63, tile = (r >> 6) & 3, k = r >> 8;                 // k < 121
+        const int o = 32 * tile + pack_perm(lane & 31), ki = 16 * k + 8 * (lane >> 5);    // ki + 7 < 1936
+        uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (o < 121) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(A.pfc_w[(size_t)(ki + e) * 121 + o]);
+        }
+        A.o_dense_wp[r] = pack_row(h);
+        return;
+    }
+    r -= kRowsWp;
+    if (r < kRowsWv) {                           // [k-step][out tile][lane]: vfc1 [484][64], K padded to 496 with zeros
+        const int lane = r & 63, tile = (r >> 6) & 1, k = r >> 7;                 // k < 31
+        const int o = 32 * tile + pack_perm(lane & 31), ki = 16 * k + 8 * (lane >> 5);    // o < 64
+        uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (ki + e < 484) h[e] = pack_bf16(A.vfc1_w[(size_t)(ki + e) * 64 + o]);
+        A.o_dense_wv[r] = pack_row(h);
+        return;
+    }
+    r -= kRowsWv;
+    if (r < 121) { A.o_dense_pb[r] = pack_bf16_f32(A.pfc_b[r]); return; }        // (words 121..127 keep the -1e30 af_tower_set_dense wrote)
+    r -= 121;
+    if (r < 64) { A.o_dense_vb1[r] = pack_bf16_f32(A.vfc1_b[r]); return; }
+    r -= 64;
+    if (r < 64) { A.o_dense_vw2[r] = pack_bf16_f32(A.vfc2_w[r]); return; }
+    r -= 64;
+    if (r < 1) A.o_dense_vb2[0] = pack_bf16_f32(A.vfc2_b[0]);
 }
 
 // ------------------------------------------------------------------ host ------------------------------------------------------------------
@@ -926,8 +1077,7 @@ struct af_tower {
     uint4* heads_a = nullptr;     // af_tower_heads_mfma_kernel: A fragments
     float* heads_b32 = nullptr;   // ... and its 32 biases
     uint4 *dense_wp = nullptr, *dense_wv = nullptr;     // af_tower_dense_kernel: packed policy / value fc1 weights
-    float *dense_pb = nullptr, *dense_vb1 = nullptr, *dense_vw2 = nullptr;
-    float dense_vb2 = 0.0f;
+    float *dense_pb = nullptr, *dense_vb1 = nullptr, *dense_vw2 = nullptr, *dense_vb2 = nullptr;
 };
 
 static uint16_t bf16_rne(float f) {
@@ -998,7 +1148,7 @@ const char* af_tower_strerror(int code) {
         case AF_TOWER_OK: return "ok";
         case AF_TOWER_ERR_ARG: return "bad argument";
         case AF_TOWER_ERR_HIP: return "HIP runtime error";
-        case AF_TOWER_ERR_STATE: return "not every block has weights";
+        case AF_TOWER_ERR_STATE: return "not every weight set has been given";
         default: return "unknown error";
     }
 }
@@ -1040,6 +1190,7 @@ void af_tower_destroy(af_tower* t) {
     if (t->dense_pb) (void)hipFree(t->dense_pb);
     if (t->dense_vb1) (void)hipFree(t->dense_vb1);
     if (t->dense_vw2) (void)hipFree(t->dense_vw2);
+    if (t->dense_vb2) (void)hipFree(t->dense_vb2);
     delete t;
 }
 
@@ -1128,19 +1279,20 @@ int af_tower_set_dense(af_tower* t, const float* vfc1_w, const float* vfc1_b, co
     std::vector<float> pb(128, -1.0e30f), vb1(vfc1_b, vfc1_b + 64), vw2(64);
     for (int o = 0; o < 121; ++o) pb[o] = bf16_round(pfc_b[o]);
     for (int o = 0; o < 64; ++o) { vb1[o] = bf16_round(vfc1_b[o]); vw2[o] = bf16_round(vfc2_w[o]); }
-    t->dense_vb2 = bf16_round(vfc2_b[0]);
+    const float vb2 = bf16_round(vfc2_b[0]);
     int rc = upload(&t->dense_wp, wp.data(), wp.size() * 2);
     if (!rc) rc = upload(&t->dense_wv, wv.data(), wv.size() * 2);
     if (!rc) rc = upload(&t->dense_pb, pb.data(), pb.size() * 4);
     if (!rc) rc = upload(&t->dense_vb1, vb1.data(), vb1.size() * 4);
     if (!rc) rc = upload(&t->dense_vw2, vw2.data(), vw2.size() * 4);
+    if (!rc) rc = upload(&t->dense_vb2, &vb2, 4);
     return rc;
 }
 
 int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* pin_dev, float* policy_dev, float* value_dev,
                    int32_t batch) {
     if (!t || !vin_dev || !pin_dev || !policy_dev || !value_dev || batch < 1) return AF_TOWER_ERR_ARG;
-    if (!t->dense_wp) return AF_TOWER_ERR_STATE;
+    if (!t->dense_wp || !t->dense_vb2) return AF_TOWER_ERR_STATE;
     DenseArgs a;
     a.vin = static_cast<const __bf16*>(vin_dev); a.pin = static_cast<const __bf16*>(pin_dev);
     a.wp = t->dense_wp; a.wv = t->dense_wv; a.pb = t->dense_pb; a.vb1 = t->dense_vb1; a.vw2 = t->dense_vw2; a.vb2 = t->dense_vb2;
@@ -1228,6 +1380,77 @@ int af_tower_debug_cycles(unsigned long long* host) {
     return AF_TOWER_OK;
 }
 #endif
+
+// ---- weights without the host ----
+// element counts of af_tower_update_device's tensors, in its order (include/af_tower_bf16.h)
+static int64_t update_count(int i, int blocks) {
+    static const int64_t kBlock[6] = {147456, 128, 147456, 128, 16384, 128};
+    static const int64_t kTail[10] = {512, 4, 2048, 16, 30976, 64, 64, 1, 234256, 121};
+    if (i == 0) return 9600;
+    if (i == 1) return 128;
+    if (i < 2 + 6 * blocks) return kBlock[(i - 2) % 6];
+    return kTail[i - 2 - 6 * blocks];
+}
+
+static bool all_set(const af_tower* t) {
+    for (char c : t->set) if (!c) return false;
+    return t->stem_w && t->stem_b && t->heads_w && t->heads_b && t->heads_a && t->heads_b32 && t->dense_wp && t->dense_wv &&
+           t->dense_pb && t->dense_vb1 && t->dense_vw2 && t->dense_vb2;
+}
+
+int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_ptrs, const int64_t* counts, int32_t n) {
+    // all or nothing: everything is checked before the first launch
+    if (!t || !dev_ptrs || !counts || n != 12 + 6 * t->blocks) return AF_TOWER_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (!dev_ptrs[i] || counts[i] != update_count(i, t->blocks)) return AF_TOWER_ERR_ARG;
+    if (!all_set(t)) return AF_TOWER_ERR_STATE;                  // the host setters allocate the buffers: nothing to write into yet
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int b0 = 0; b0 < t->blocks; b0 += kPackBlocks) {
+        const int nb = t->blocks - b0 < kPackBlocks ? t->blocks - b0 : kPackBlocks;
+        PackBlocksArgs a = {};
+        for (int j = 0; j < nb; ++j) {
+            for (int k = 0; k < 6; ++k) a.src[j][k] = dev_ptrs[2 + 6 * (b0 + j) + k];
+            a.w1[j] = t->w1[b0 + j]; a.w2[j] = t->w2[b0 + j]; a.b1[j] = t->b1[b0 + j]; a.b2[j] = t->b2[b0 + j];
+        }
+        hipLaunchKernelGGL(af_tower_pack_blocks_kernel, dim3(kPackBlockThreads / 256, nb), dim3(256), 0, st, a);
+    }
+    const float* const* e = dev_ptrs + 2 + 6 * t->blocks;
+    PackEndsArgs a;
+    a.stem_w = dev_ptrs[0]; a.stem_b = dev_ptrs[1];
+    a.vconv_w = e[0]; a.vconv_b = e[1]; a.pconv_w = e[2]; a.pconv_b = e[3];
+    a.vfc1_w = e[4]; a.vfc1_b = e[5]; a.vfc2_w = e[6]; a.vfc2_b = e[7]; a.pfc_w = e[8]; a.pfc_b = e[9];
+    a.o_stem_w = t->stem_w; a.o_stem_b = t->stem_b; a.o_heads_w = t->heads_w; a.o_heads_b = t->heads_b;
+    a.o_heads_a = t->heads_a; a.o_heads_b32 = t->heads_b32; a.o_dense_wp = t->dense_wp; a.o_dense_wv = t->dense_wv;
+    a.o_dense_pb = t->dense_pb; a.o_dense_vb1 = t->dense_vb1; a.o_dense_vw2 = t->dense_vw2; a.o_dense_vb2 = t->dense_vb2;
+    hipLaunchKernelGGL(af_tower_pack_ends_kernel, dim3((kPackEndsThreads + 255) / 256), dim3(256), 0, st, a);
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
+
+int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes) {
+    if (!t || index < 0 || index >= 4 * t->blocks + 12) return AF_TOWER_ERR_ARG;
+    const void* p = nullptr;
+    int64_t bytes = 0;
+    if (index < 4 * t->blocks) {
+        const int b = index / 4;
+        const void* const ptr[4] = {t->w1[b], t->w2[b], t->b1[b], t->b2[b]};
+        const int64_t size[4] = {(int64_t)kRowsW1 * 16, (int64_t)kRowsW2 * 16, 128 * 4, 128 * 4};
+        p = ptr[index % 4]; bytes = size[index % 4];
+    } else {
+        const void* const ptr[12] = {t->stem_w, t->stem_b, t->heads_w, t->heads_b, t->heads_a, t->heads_b32,
+                                     t->dense_wp, t->dense_wv, t->dense_pb, t->dense_vb1, t->dense_vw2, t->dense_vb2};
+        const int64_t size[12] = {(int64_t)kRowsStem * 16, 128 * 4, 20 * 128 * 4, 20 * 4, (int64_t)kRowsHeadsA * 16, 32 * 4,
+                                  (int64_t)kRowsWp * 16, (int64_t)kRowsWv * 16, 128 * 4, 64 * 4, 64 * 4, 4};
+        p = ptr[index - 4 * t->blocks]; bytes = size[index - 4 * t->blocks];
+    }
+    if (!p) return AF_TOWER_ERR_STATE;                           // its host setter has not run yet
+    if (!host_out) return bytes;
+    if (cap_bytes < bytes) return AF_TOWER_ERR_ARG;
+    TW_HIP_OK(hipSetDevice(t->device));
+    TW_HIP_OK(hipDeviceSynchronize());
+    TW_HIP_OK(hipMemcpy(host_out, p, (size_t)bytes, hipMemcpyDeviceToHost));
+    return bytes;
+}
 
 int64_t af_tower_flops_per_position(const af_tower* t) {
     return (int64_t)2 * t->blocks * (128 * 128 * 9 * 2 + 128 * 128) * kNPIX;

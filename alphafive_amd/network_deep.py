@@ -7,9 +7,27 @@ all-PyTorch reference path.  Performance-only configuration (no che
 it, random init, no bit parity); it plugs into SelfPlayEngine through the same
 planes[G,3,S,S] -> (prob[G,C], value[G]) evaluator seam as the fp32 net.
 """
+import collections
+
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+
+def variable_shapes(board_size, blocks=8, width=128):
+    """{name: shape}, ordered as af_tower_update_device takes the tensors (include/af_tower_bf16.h; tower_hip.update_names):
+    kernels OIHW, dense layers [in][out].  Every bias name contains "bias" (train.loss_terms leaves those out of its L2 term)."""
+    C, w = board_size * board_size, width
+    shapes = collections.OrderedDict()
+    shapes["stem/kernel"], shapes["stem/bias"] = (w, 3, 5, 5), (w,)
+    for b in range(blocks):
+        for layer, k in (("conv1", 3), ("conv2", 3), ("res", 1)):
+            shapes["tower/block%d_%s/kernel" % (b, layer)] = (w, w, k, k)
+            shapes["tower/block%d_%s/bias" % (b, layer)] = (w,)
+    for layer, kshape in (("value/conv", (4, w, 1, 1)), ("policy/conv", (16, w, 1, 1)), ("value/fc1", (4 * C, 64)),
+                          ("value/fc2", (64, 1)), ("policy/fc", (16 * C, C))):
+        shapes[layer + "/kernel"], shapes[layer + "/bias"] = kshape, (kshape[0],) if len(kshape) == 4 else (kshape[1],)
+    return shapes
 
 
 class _HipEvaluator(object):
@@ -52,6 +70,91 @@ class DeepResNet(object):
         self.vconv, self.pconv = (glorot(4, width, 1, 1), z(4)), (glorot(16, width, 1, 1), z(16))
         self.vfc1, self.vfc2 = (glorot(4 * C, 64), z(64)), (glorot(64, 1), z(1))
         self.pfc = (glorot(16 * C, C), z(C))
+
+    # ---- weights by name ----
+    def variable_shapes(self):
+        return variable_shapes(self.board_size, self.blocks, self.width)
+
+    def _named(self):
+        """name -> (holder, key, index) of the tensor behind it: self.stem / self.tower[b][...] / the heads stay the storage
+        (callers replace those tuples directly), so a name is resolved when it is used."""
+        out = collections.OrderedDict()
+        out["stem/kernel"], out["stem/bias"] = (self.__dict__, "stem", 0), (self.__dict__, "stem", 1)
+        for b, blk in enumerate(self.tower):
+            for layer, key in (("conv1", "c1"), ("conv2", "c2"), ("res", "res")):
+                out["tower/block%d_%s/kernel" % (b, layer)] = (blk, key, 0)
+                out["tower/block%d_%s/bias" % (b, layer)] = (blk, key, 1)
+        for layer, key in (("value/conv", "vconv"), ("policy/conv", "pconv"), ("value/fc1", "vfc1"), ("value/fc2", "vfc2"),
+                           ("policy/fc", "pfc")):
+            out[layer + "/kernel"], out[layer + "/bias"] = (self.__dict__, key, 0), (self.__dict__, key, 1)
+        return out
+
+    def _tensor(self, ref):
+        holder, key, i = ref
+        return holder[key][i]
+
+    @property
+    def variables(self):
+        """{name: float32 host array} in variable_shapes() order: the values the evaluators use (bf16-rounded on a bf16 net)."""
+        return collections.OrderedDict((k, self._tensor(r).detach().float().cpu().numpy().copy()) for k, r in self._named().items())
+
+    def _checked(self, variables):
+        shapes = self.variable_shapes()
+        for name, shape in shapes.items():
+            if name not in variables:
+                raise KeyError("missing variable %s" % name)
+            if tuple(variables[name].shape) != tuple(shape):
+                raise ValueError("variable %s has shape %s, expected %s" % (name, tuple(variables[name].shape), tuple(shape)))
+        return shapes
+
+    def set_variables(self, variables):
+        """The host path: values (arrays or tensors, variable_shapes() names and shapes) -> the net's tensors in self.dtype; if a hip
+        backend is selected its tower is rebuilt from them through the host setters (the evaluator handed out stays valid)."""
+        new = {}
+        for name in self._checked(variables):
+            v = variables[name]
+            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32))
+            new[name] = v.to(device=self.device, dtype=self.dtype).contiguous()
+        for name, (holder, key, i) in self._named().items():
+            pair = list(holder[key])
+            pair[i] = new[name]
+            holder[key] = tuple(pair)
+        old = getattr(self, "_tower", None)
+        if old is not None:
+            self.select_backend("hip", old.max_batch)
+            self._tower.bind_outputs(old.policy, old.value)         # outputs an engine had bound stay bound
+            old.close()
+
+    @torch.no_grad()
+    def set_variables_device(self, tensors):
+        """set_variables without the host: `tensors` maps every name to a float32 tensor (a deep Trainer's parameters:
+        train.Trainer.device_variables()).  With a hip backend selected the net's own tensors take the values in self.dtype in place
+        (one copy_ per variable, so eval_device follows), and HipTower.load_device packs in place, stream-ordered, with no wait:
+        the kernels straight from the caller's tensors — the packed buffers are the snapshot, no weight tensor is cloned — and the
+        biases from small fp32 temporaries made of the net's rounded copies.  The tower adds the stem's, blocks' and head
+        convolutions' biases in fp32 as given, so handing over the rounded values is what makes host path and device path pack
+        the same values and give the same bits.  A cpu net, or one without a hip backend, does what set_variables does."""
+        tower = getattr(self, "_tower", None)
+        if self.device.type != "cuda" or tower is None:
+            self.set_variables(tensors)
+            return
+        src = collections.OrderedDict()
+        for name in self._checked(tensors):
+            src[name] = tensors[name].detach().to(device=self.device, dtype=torch.float32).contiguous()   # no copy if it already is
+        for name, ref in self._named().items():
+            own = self._tensor(ref)
+            own.copy_(src[name])
+            if name.endswith("bias"):
+                src[name] = own.float()
+        tower.load_device(src)
+        self._pack_version = getattr(self, "_pack_version", 0) + 1
+
+    def save_npz(self, path):
+        np.savez(path, **self.variables)
+
+    def load_npz(self, path):
+        with np.load(path) as z:
+            self.set_variables({k: z[k] for k in z.files})
 
     def flops_per_position(self):
         HW, w = self.board_size ** 2, self.width

@@ -12,7 +12,12 @@ _lib = None
 
 
 class TowerError(RuntimeError):
-    pass
+    """`code`: the AF_TOWER_ERR_* value of include/af_tower_bf16.h the library returned; AF_TOWER_ERR_ARG (-1) for what the binding
+    itself refuses before calling in (a missing tensor, a wrong count, dtype, layout or device)."""
+
+    def __init__(self, message, code=-1):
+        super().__init__(message)
+        self.code = int(code)
 
 
 def lib():
@@ -40,6 +45,9 @@ def lib():
         L.af_tower_flops_per_position.argtypes = [vp]
         L.af_tower_flops_per_position.restype = C.c_int64
         L.af_tower_tune.argtypes = [C.c_int32, C.c_int32]
+        L.af_tower_update_device.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_int64), C.c_int32]
+        L.af_tower_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
+        L.af_tower_debug_weights.restype = C.c_int64
         L.af_tower_strerror.argtypes = [C.c_int]
         L.af_tower_strerror.restype = C.c_char_p
         _lib = L
@@ -48,7 +56,17 @@ def lib():
 
 def _check(rc, what):
     if rc < 0:
-        raise TowerError(f"{what}: {lib().af_tower_strerror(rc).decode()} (code {rc})")
+        raise TowerError(f"{what}: {lib().af_tower_strerror(rc).decode()} (code {rc})", rc)
+
+
+def update_names(blocks):
+    """The tensors of af_tower_update_device in its order (include/af_tower_bf16.h), by DeepResNet's variable names."""
+    names = ["stem/kernel", "stem/bias"]
+    for b in range(blocks):
+        names += ["tower/block%d_%s/%s" % (b, layer, part) for layer in ("conv1", "conv2", "res") for part in ("kernel", "bias")]
+    for layer in ("value/conv", "policy/conv", "value/fc1", "value/fc2", "policy/fc"):
+        names += [layer + "/kernel", layer + "/bias"]
+    return names
 
 
 def tune(key, value):
@@ -61,26 +79,18 @@ class HipTower(object):
     def __init__(self, blocks, board_size, width, max_batch, device, stem=None, vconv=None, pconv=None, dense=None):
         self.S, self.width, self.max_batch, self.device = board_size, width, max_batch, torch.device(device)
         self._h = C.c_void_p()
+        self.blocks = len(blocks)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _check(lib().af_tower_create(board_size, width, len(blocks), idx, C.byref(self._h)), "af_tower_create")
-        fp = C.POINTER(C.c_float)
-
-        def host(t):
-            a = np.ascontiguousarray(t.detach().float().cpu().numpy(), np.float32)
-            return a, a.ctypes.data_as(fp)
         for b, blk in enumerate(blocks):
-            keep = [host(blk[k][i]) for k in ("c1", "c2", "res") for i in (0, 1)]
-            _check(lib().af_tower_set_block(self._h, b, *[p for _, p in keep]), f"af_tower_set_block({b})")
+            self.set_block(b, blk)
         if stem is not None:
-            (_, wp), (_, bp) = keep = [host(stem[0]), host(stem[1])]
-            _check(lib().af_tower_set_stem(self._h, wp, bp), "af_tower_set_stem")
+            self.set_stem(stem)
         if vconv is not None:
-            keep = [host(t) for t in (vconv[0], vconv[1], pconv[0], pconv[1])]
-            _check(lib().af_tower_set_heads(self._h, *[p for _, p in keep]), "af_tower_set_heads")
+            self.set_heads(vconv, pconv)
         self.has_dense = dense is not None
         if dense is not None:                          # (vfc1_w [4C][64], vfc1_b, vfc2_w [64][1], vfc2_b, pfc_w [16C][C], pfc_b)
-            keep = [host(t) for t in dense]
-            _check(lib().af_tower_set_dense(self._h, *[p for _, p in keep]), "af_tower_set_dense")
+            self.set_dense(dense)
         self.policy = torch.empty((max_batch, board_size ** 2), dtype=torch.float32, device=self.device)
         self.value = torch.empty((max_batch,), dtype=torch.float32, device=self.device)
         self.vin = torch.empty((max_batch, 4 * board_size ** 2), dtype=torch.bfloat16, device=self.device)
@@ -92,6 +102,29 @@ class HipTower(object):
         self.g = torch.zeros_like(self.x)
         S = board_size
         self._xin = self.x[:, :, S:S + S * S, :].unflatten(2, (S, S))      # [B, width/8, S, S, 8] view of the board pixels
+
+    # ---- host setters: fp32 host copies, packed by the library's host loops, buffers re-created (not stream-ordered) ----
+    @staticmethod
+    def _host(tensors):
+        keep = [np.ascontiguousarray(t.detach().float().cpu().numpy(), np.float32) for t in tensors]
+        return keep, [a.ctypes.data_as(C.POINTER(C.c_float)) for a in keep]
+
+    def set_block(self, b, blk):
+        keep, ptrs = self._host([blk[k][i] for k in ("c1", "c2", "res") for i in (0, 1)])
+        _check(lib().af_tower_set_block(self._h, b, *ptrs), f"af_tower_set_block({b})")
+
+    def set_stem(self, stem):
+        keep, ptrs = self._host(stem)
+        _check(lib().af_tower_set_stem(self._h, *ptrs), "af_tower_set_stem")
+
+    def set_heads(self, vconv, pconv):
+        keep, ptrs = self._host((vconv[0], vconv[1], pconv[0], pconv[1]))
+        _check(lib().af_tower_set_heads(self._h, *ptrs), "af_tower_set_heads")
+
+    def set_dense(self, dense):
+        keep, ptrs = self._host(dense)
+        _check(lib().af_tower_set_dense(self._h, *ptrs), "af_tower_set_dense")
+        self.has_dense = True
 
     def load_nchw(self, h):
         """h: bf16 [B, width, S, S] -> interior of the C8 buffer."""
@@ -130,6 +163,47 @@ class HipTower(object):
     def forward(self, B):
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().af_tower_forward(self._h, stream, self.x.data_ptr(), self.g.data_ptr(), B), "af_tower_forward")
+
+    def load_device(self, tensors):
+        """Weight update without the host (af_tower_update_device): `tensors` is a list in the ABI's order or a dict by the names
+        of update_names(blocks); each a contiguous float32 tensor on this handle's device, OIHW convolutions and [in][out] dense
+        layers.  Kernels re-pack them in place into the buffers the handle owns, on torch's current stream, behind the forwards
+        already queued there: launches only, no wait, legal inside a stream capture.  The tensors must hold their values until
+        the pack kernels have run — a producer on the same stream is ordered."""
+        names = update_names(self.blocks)
+        if isinstance(tensors, dict):
+            missing = [k for k in names if k not in tensors]
+            if missing:
+                raise TowerError("load_device: missing %s" % ", ".join(missing))
+            tensors = [tensors[k] for k in names]
+        tensors = list(tensors)
+        if len(tensors) != len(names):
+            raise TowerError("load_device: %d tensors, expected %d (12 + 6 * blocks)" % (len(tensors), len(names)))
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        for name, t in zip(names, tensors):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise TowerError(f"load_device({name}): a contiguous float32 tensor on {self.device} is required")
+            if t.device.index != idx:
+                raise TowerError(f"load_device({name}): tensor on {t.device}, handle on {self.device}")
+        n = len(names)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_update_device(self._h, stream, (C.c_void_p * n)(*[t.data_ptr() for t in tensors]),
+                                            (C.c_int64 * n)(*[t.numel() for t in tensors]), n), "af_tower_update_device")
+
+    def debug_weights(self):
+        """Tests: every weight-derived device buffer of the handle as bytes, in af_tower_debug_weights' order (synchronises);
+        None for a buffer whose host setter has not run."""
+        out = []
+        for i in range(4 * self.blocks + 12):
+            size = lib().af_tower_debug_weights(self._h, i, None, 0)
+            if size == -3:                              # AF_TOWER_ERR_STATE
+                out.append(None)
+                continue
+            _check(size, "af_tower_debug_weights")
+            buf = np.empty(size, np.uint8)
+            _check(lib().af_tower_debug_weights(self._h, i, buf.ctypes.data_as(C.c_void_p), size), "af_tower_debug_weights")
+            out.append(buf)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -41,9 +41,32 @@ def forward_train(params, x):
     return p @ params["policy/fc/kernel"] + params["policy/fc/bias"], v
 
 
-def loss_terms(params, boards, distrib, winner, weights):
-    """network.py:40-50 -> dict(total, cross_entropy, value_loss, entropy)."""
-    logits, value = forward_train(params, boards)
+def forward_train_deep(params, x):
+    """Differentiable forward of network_deep.DeepResNet on its named parameters (network_deep.variable_shapes: OIHW kernels,
+    [in][out] dense layers; the block count is read off the names) -> (logits[B,S*S], value[B]).  The torch ops of
+    DeepResNet.eval_device in the same order, so on fp32 parameters it gives eval_device(dtype=float32)'s bits."""
+    def wb(name):
+        return params[name + "/kernel"], params[name + "/bias"]
+
+    B = x.shape[0]
+    h = F.elu(F.conv2d(x, *wb("stem"), padding=2))
+    b = 0
+    while "tower/block%d_res/kernel" % b in params:
+        r = F.conv2d(h, *wb("tower/block%d_res" % b))
+        g = F.elu(F.conv2d(h, *wb("tower/block%d_conv1" % b), padding=1))
+        h = F.elu(r + F.conv2d(g, *wb("tower/block%d_conv2" % b), padding=1))
+        b += 1
+    v = F.elu(F.conv2d(h, *wb("value/conv"))).reshape(B, -1)
+    v = F.elu(v @ params["value/fc1/kernel"] + params["value/fc1/bias"])
+    v = torch.tanh((v @ params["value/fc2/kernel"] + params["value/fc2/bias"]).float() / 2).squeeze(1)
+    p = F.elu(F.conv2d(h, *wb("policy/conv"))).reshape(B, -1)
+    return (p @ params["policy/fc/kernel"] + params["policy/fc/bias"]).float(), v
+
+
+def loss_terms(params, boards, distrib, winner, weights, forward=forward_train):
+    """network.py:40-50 -> dict(total, cross_entropy, value_loss, entropy).  `forward`: (params, boards) -> (logits, value),
+    the 42-variable net's by default, forward_train_deep for network_deep.DeepResNet."""
+    logits, value = forward(params, boards)
     logsm = F.log_softmax(logits, dim=1)
     x_entropy = (distrib * logsm).sum(dim=1)
     value_sq = (value - winner) ** 2
@@ -58,10 +81,13 @@ class Trainer(object):
     multi-tensor launches instead of ~210 per-variable ones (at the reference's batch of 512 the step is launch-bound:
     7.4 -> 6.0 ms, tools/probe_train_step.py); step(..., metrics=False) returns None and never waits for the device."""
 
-    def __init__(self, variables, board_size, device=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    def __init__(self, variables, board_size, device=None, beta1=0.9, beta2=0.999, eps=1e-8, forward=None, shapes=None):
+        """`forward` / `shapes`: the differentiable forward and the {name: shape} table of the net to train; by default the
+        42-variable net's (forward_train, network.variable_shapes).  DeepResNet: forward_train_deep, net.variable_shapes()."""
         self.board_size = board_size
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
-        shapes = variable_shapes(board_size)
+        self.forward = forward if forward is not None else forward_train
+        shapes = shapes if shapes is not None else variable_shapes(board_size)
         self.params = {k: torch.tensor(np.asarray(variables[k], np.float32), device=self.device, requires_grad=True)
                        for k in shapes}
         self.m = {k: torch.zeros_like(p) for k, p in self.params.items()}
@@ -73,7 +99,7 @@ class Trainer(object):
     def _update(self, batch):
         """loss -> gradients -> Adam (tf.train.AdamOptimizer: lr_t folds the bias corrections, eps is added to sqrt(v)).
         Same arithmetic order as the per-variable loop it replaces: p -= (lr_t * m) / (sqrt(v) + eps)."""
-        terms = loss_terms(self.params, *batch)
+        terms = loss_terms(self.params, *batch, forward=self.forward)
         ps = list(self.params.values())
         grads = list(torch.autograd.grad(terms["total"], ps))
         ms, vs = list(self.m.values()), list(self.v.values())
@@ -186,7 +212,9 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step
 
     weights_on_device=True hands the new weights to the engine's evaluator without the host: net.set_variables_device(
     trainer.device_variables()) snapshots the parameters on the device and the evaluator re-packs them in place
-    (af_net_update_device) instead of 42 device-to-host copies, a host re-pack and a reallocation of the evaluator per step."""
+    (af_net_update_device) instead of 42 device-to-host copies, a host re-pack and a reallocation of the evaluator per step.
+    `net` may be a network_deep.DeepResNet with a Trainer built on forward_train_deep: its set_variables_device re-packs the
+    bf16 tower in place (af_tower_update_device: launches only)."""
     step = start_step
     on_device = hasattr(stack, "iter_push_packed") and hasattr(engine, "post_episodes_device")
     cap = 256

@@ -28,7 +28,7 @@ typedef struct af_tower af_tower;
 #define AF_TOWER_OK 0
 #define AF_TOWER_ERR_ARG   (-1)
 #define AF_TOWER_ERR_HIP   (-2)
-#define AF_TOWER_ERR_STATE (-3)   /* forward before every block was set */
+#define AF_TOWER_ERR_STATE (-3)   /* forward / device update before the weights it needs were set through the host setters */
 
 /* board_size must be 11 and width 128 in this build (4 waves x 32 output channels, 4 pixel tiles). */
 int af_tower_create(int32_t board_size, int32_t width, int32_t blocks, int32_t device, af_tower** out);
@@ -65,6 +65,36 @@ int af_tower_set_dense(af_tower* t, const float* vfc1_w, const float* vfc1_b, co
                        const float* pfc_w, const float* pfc_b);
 int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* pin_dev, float* policy_dev, float* value_dev,
                    int32_t batch);
+
+/* Weight update without the host.  Kernels read fp32 weights from DEVICE memory — the layouts the host setters above take: OIHW
+ * convolutions, [in][out] dense layers — and write, in place, every weight-derived buffer the handle owns (fragment streams,
+ * biases, b2 = c2_b + res_b, the bf16-rounded dense biases and the fc2 bias word), byte for byte what the host setters make of
+ * the same values.  dev_ptrs / counts hold n = 12 + 6 * blocks entries in this fixed order:
+ *     stem_w, stem_b,
+ *     per block: c1_w, c1_b, c2_w, c2_b, res_w, res_b,
+ *     vconv_w, vconv_b, pconv_w, pconv_b,
+ *     vfc1_w, vfc1_b, vfc2_w, vfc2_b, pfc_w, pfc_b
+ * with element counts stem_w 9600, every 128-wide bias 128, c1_w / c2_w 147456, res_w 16384, vconv_w / vconv_b 512 / 4,
+ * pconv_w / pconv_b 2048 / 16, vfc1_w / vfc1_b 30976 / 64, vfc2_w / vfc2_b 64 / 1, pfc_w / pfc_b 234256 / 121.
+ * All or nothing, checked before the first launch: a null handle, array or entry, a wrong n or a wrong count is
+ * AF_TOWER_ERR_ARG; a handle whose stem, heads, dense layers and every block have not been set once through the host setters
+ * (they allocate the buffers) is AF_TOWER_ERR_STATE.
+ * The call is launches only, stream-ordered on `stream`: nothing is freed, allocated or copied to the host, nothing waits, the
+ * pointer table travels in kernel arguments (the arrays may go as soon as the call returns; the tensors must hold their values
+ * until the kernels have run).  bf16 needs no per-layer scales, so — unlike af_net_update_device — there is nothing to read back.
+ * It is therefore legal under stream capture, and since every buffer keeps its address and no weight-derived value is a
+ * by-value kernel argument:
+ *   - a forward graph captured before an update sees the new weights when it is replayed after it;
+ *   - [update; forward] may itself be captured and replayed over changed source tensors.
+ * A host setter called later replaces (frees and re-creates) its buffers: graphs captured over the handle are stale then. */
+int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_ptrs, const int64_t* counts, int32_t n);
+
+/* Tests: weight-derived device buffer `index` copied to host_out; returns its size in bytes (also with host_out NULL, which
+ * copies nothing), AF_TOWER_ERR_ARG past the last index or if cap_bytes is too small, AF_TOWER_ERR_STATE for a buffer whose
+ * host setter has not run.  Synchronises the device.  4 * blocks + 12 buffers:
+ *   4b + 0..3 = w1, w2, b1, b2 of block b; then stem_w, stem_b, heads_w, heads_b, heads_a, heads_b32, dense_wp, dense_wv,
+ *   dense_pb, dense_vb1, dense_vw2, dense_vb2. */
+int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes);
 
 /* A/B knobs (process-global): key 0 = B-fragment ring depth (0 = per-kernel default, 8, 12, 16), key 1 = persistent
  * workgroups (0 = one per CU), key 2 = profiling ablation bits (results wrong by design: 1 no re-staging, 2 no stores;
