@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "af_noise.h"
 #include "af_replay.h"
 
 #define RP_HIP_OK(expr)                                      \
@@ -86,6 +87,138 @@ __global__ __launch_bounds__(256) void af_replay_sample_kernel(SampleArgs A) {
     if (threadIdx.x == 0) {
         A.out_weights[b] = A.weights[slot];
         A.out_values[b] = A.values[slot];
+    }
+}
+
+// Device-drawn minibatches (include/af_replay.h, af_replay_sample_device; the numpy statement the kernel is held to bit for bit
+// is alphafive_amd/replay.py:draw_reference).  Logical position i of minibatch b owns the Philox4x32-10 block
+//   v = af_philox4x32(i, b, draw, AF_REPLAY_DRAW_TAG, seed lo, seed hi):  v[0] = its sort word, v[1] >> 30 = quarter turns, v[2] >> 31 = flip,
+// and the minibatch is the k positions with the smallest composite v[0] << 32 | i in ascending order.
+struct DrawArgs {
+    int32_t* sel;                // [3][total]: physical slot, quarter turns, flip (what af_replay_sample_kernel reads)
+    int32_t* draws;              // [3][total]: logical index, quarter turns, flip; may be null
+    int64_t head;
+    uint32_t k0, k1, draw;
+    int n, k, cap, total;        // n stored positions, k = samples per minibatch (1 <= k <= n, k <= AF_REPLAY_MAX_DRAW), total = batches * k
+};
+
+__device__ __forceinline__ af_u32x4 draw_block(const DrawArgs& A, uint32_t i, uint32_t b) {
+    return af_philox4x32(i, b, A.draw, AF_REPLAY_DRAW_TAG, A.k0, A.k1);
+}
+
+// One 256-thread workgroup (4 waves) per minibatch; thread t owns positions t, t + 256, ...  Exact selection, nothing stored per
+// position: the words are recomputed in every pass (~100 VALU operations each; at n = 12000 that is 47 per thread and pass).
+//   1. radix select of the k-th smallest word T, 4 passes of 8 bits: LDS histogram of the digit among the words that match the
+//      digits already fixed, then every wave finds the bin by a prefix over the 256 counts (lane l holds bins 4l .. 4l+3);
+//   2. compaction of the composites into LDS: every word < T, and of the words == T the `need` lowest indices — all of them
+//      when there are exactly `need` (then the order of arrival does not matter), else by rank in index order, 256 positions a round;
+//   3. bitonic sort of next_pow2(k) composites, padded with all-ones;
+//   4. entry j of the sorted array is sample j: one more Philox of the winner gives its turns and flip.
+// Every index formed is bounded: positions by n, LDS slots by k <= AF_REPLAY_MAX_DRAW, bins by 256, outputs by total, slots by cap.
+__global__ __launch_bounds__(256) void af_replay_draw_kernel(DrawArgs A) {
+    __shared__ unsigned long long comp[AF_REPLAY_MAX_DRAW];      // 32 KB
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t wave_hits[4];
+    __shared__ uint32_t fill;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t n = (uint32_t)A.n, k = (uint32_t)A.k;
+
+    uint32_t T = 0, need = k, ties = 0;          // `need`: rank (from 1) of the wanted word among those matching the fixed digits of T
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t fixed = pass ? 0xFFFFFFFFu << (shift + 8) : 0u;
+        hist[tid] = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += 256) {
+            const uint32_t w = draw_block(A, i, b).v[0];
+            if ((w & fixed) == T) atomicAdd(&hist[(w >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const uint32_t c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+        const uint32_t own = c0 + c1 + c2 + c3;
+        uint32_t incl = own;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        const unsigned long long reach = __ballot(incl >= need);         // never empty: at least `need` words match
+        const int src = reach ? __ffsll(reach) - 1 : 63;
+        uint32_t below = __shfl(incl - own, src), bin = 4u * (uint32_t)src;
+        const uint32_t s0 = __shfl(c0, src), s1 = __shfl(c1, src), s2 = __shfl(c2, src), s3 = __shfl(c3, src);
+        ties = s0;
+        if (below + ties < need) {
+            below += ties; ties = s1; ++bin;
+            if (below + ties < need) {
+                below += ties; ties = s2; ++bin;
+                if (below + ties < need) { below += ties; ties = s3; ++bin; }
+            }
+        }
+        T |= bin << shift;
+        need -= below;
+        __syncthreads();                                                 // the next pass clears the histogram
+    }
+    // now: k - need words are < T, `ties` words are == T, and need <= ties of those are wanted
+    const uint32_t n_less = k - need;
+    const bool all_ties = need >= ties;
+    if (tid == 0) fill = 0;
+    for (uint32_t j = tid; j < AF_REPLAY_MAX_DRAW; j += 256) comp[j] = ~0ull;
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += 256) {
+        const uint32_t w = draw_block(A, i, b).v[0];
+        if (w < T || (all_ties && w == T)) {
+            const uint32_t pos = atomicAdd(&fill, 1u);
+            if (pos < k) comp[pos] = ((unsigned long long)w << 32) | i;
+        }
+    }
+    if (!all_ties) {                             // equal words at the threshold: the lowest indices win (block-uniform branch)
+        uint32_t taken = 0;
+        for (uint32_t i0 = 0; i0 < n && taken < need; i0 += 256) {
+            const uint32_t i = i0 + tid;
+            const bool hit = i < n && draw_block(A, i, b).v[0] == T;
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0) wave_hits[wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t rank = taken, round = 0;
+            for (uint32_t w = 0; w < 4; ++w) {
+                const uint32_t c = wave_hits[w];
+                if (w < wave) rank += c;
+                round += c;
+            }
+            rank += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (hit && rank < need) comp[n_less + rank] = ((unsigned long long)T << 32) | i;       // n_less + rank < k
+            taken += round;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    uint32_t P = 1;
+    while (P < k) P <<= 1;
+    for (uint32_t size = 2; size <= P; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t t = tid; t < (P >> 1); t += 256) {
+                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;          // hi < P <= AF_REPLAY_MAX_DRAW
+                const unsigned long long x = comp[lo], y = comp[hi];
+                if ((x > y) == ((lo & size) == 0)) { comp[lo] = y; comp[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+
+    for (uint32_t j = tid; j < k; j += 256) {
+        uint32_t i = (uint32_t)comp[j];
+        if (i >= n) i = n - 1;                   // cannot happen: exactly k composites were placed
+        const af_u32x4 v = draw_block(A, i, b);
+        const size_t o = (size_t)b * k + j, total = (size_t)A.total;
+        const int32_t turns = (int32_t)(v.v[1] >> 30), flip = (int32_t)(v.v[2] >> 31);
+        A.sel[o] = (int32_t)((A.head + (int64_t)i) % A.cap);
+        A.sel[total + o] = turns;
+        A.sel[2 * total + o] = flip;
+        if (A.draws) {
+            A.draws[o] = (int32_t)i;
+            A.draws[total + o] = turns;
+            A.draws[2 * total + o] = flip;
+        }
     }
 }
 
@@ -265,6 +398,26 @@ static int ensure_pinned(af_replay* r, size_t bytes) {
     r->pinned = nullptr; r->pinned_bytes = 0;
     RP_HIP_OK(hipHostMalloc(&r->pinned, bytes, hipHostMallocDefault));
     r->pinned_bytes = bytes;
+    return AF_REPLAY_OK;
+}
+
+static int ensure_sel(af_replay* r, int n) {
+    if (n <= r->sel_cap) return AF_REPLAY_OK;
+    if (r->sel) (void)hipFree(r->sel);
+    r->sel = nullptr; r->sel_cap = 0;
+    RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->sel), (size_t)3 * n * 4));
+    r->sel_cap = n;
+    return AF_REPLAY_OK;
+}
+
+// af_replay_sample_kernel over the first `num` triples of r->sel
+static int launch_sample(af_replay* r, hipStream_t st, int num, float* boards_dev, float* weights_dev, float* values_dev, float* policies_dev) {
+    SampleArgs a;
+    a.boards = r->boards; a.policies = r->policies; a.last = r->last; a.values = r->values; a.weights = r->weights;
+    a.sel = r->sel; a.out_boards = boards_dev; a.out_weights = weights_dev; a.out_values = values_dev; a.out_policies = policies_dev;
+    a.S = r->S; a.C = r->C; a.num = num;
+    hipLaunchKernelGGL(af_replay_sample_kernel, dim3(num), dim3(256), 0, st, a);
+    RP_HIP_OK(hipGetLastError());
     return AF_REPLAY_OK;
 }
 
@@ -472,12 +625,8 @@ int af_replay_sample(af_replay* r, void* stream, int32_t num, const int32_t* idx
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc = ensure_pinned(r, (size_t)3 * num * 4);
     if (rc) return rc;
-    if (num > r->sel_cap) {
-        if (r->sel) (void)hipFree(r->sel);
-        r->sel = nullptr; r->sel_cap = 0;
-        RP_HIP_OK(hipMalloc(reinterpret_cast<void**>(&r->sel), (size_t)3 * num * 4));
-        r->sel_cap = num;
-    }
+    rc = ensure_sel(r, num);
+    if (rc) return rc;
     RP_HIP_OK(hipStreamSynchronize(st));               // a previous sample's staging copy must have left the pinned buffer
     int32_t* h = static_cast<int32_t*>(r->pinned);
     for (int i = 0; i < num; ++i) {
@@ -487,13 +636,25 @@ int af_replay_sample(af_replay* r, void* stream, int32_t num, const int32_t* idx
         h[2 * num + i] = flip[i] ? 1 : 0;
     }
     RP_HIP_OK(hipMemcpyAsync(r->sel, h, (size_t)3 * num * 4, hipMemcpyHostToDevice, st));
-    SampleArgs a;
-    a.boards = r->boards; a.policies = r->policies; a.last = r->last; a.values = r->values; a.weights = r->weights;
-    a.sel = r->sel; a.out_boards = boards_dev; a.out_weights = weights_dev; a.out_values = values_dev; a.out_policies = policies_dev;
-    a.S = r->S; a.C = r->C; a.num = num;
-    hipLaunchKernelGGL(af_replay_sample_kernel, dim3(num), dim3(256), 0, st, a);
+    return launch_sample(r, st, num, boards_dev, weights_dev, values_dev, policies_dev);
+}
+
+int af_replay_sample_device(af_replay* r, void* stream, int32_t num, int32_t batches, uint64_t seed, uint32_t draw,
+                            float* boards_dev, float* weights_dev, float* values_dev, float* policies_dev, int32_t* draws_out_dev) {
+    if (!r || !boards_dev || !weights_dev || !values_dev || !policies_dev || num < 1 || batches < 1) return AF_REPLAY_ERR_ARG;
+    if (num > AF_REPLAY_MAX_DRAW || batches > AF_REPLAY_MAX_BATCHES) return AF_REPLAY_ERR_RANGE;     // (the handle is not read before this)
+    if (num > r->count) return AF_REPLAY_ERR_RANGE;
+    RP_HIP_OK(hipSetDevice(r->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int total = batches * num;                                    // <= 4096 * 4096
+    const int rc = ensure_sel(r, total);
+    if (rc) return rc;
+    DrawArgs d;
+    d.sel = r->sel; d.draws = draws_out_dev; d.head = r->head; d.k0 = (uint32_t)seed; d.k1 = (uint32_t)(seed >> 32); d.draw = draw;
+    d.n = r->count; d.k = num; d.cap = r->cap; d.total = total;
+    hipLaunchKernelGGL(af_replay_draw_kernel, dim3(batches), dim3(256), 0, st, d);
     RP_HIP_OK(hipGetLastError());
-    return AF_REPLAY_OK;
+    return launch_sample(r, st, total, boards_dev, weights_dev, values_dev, policies_dev);
 }
 
 }  // extern "C"

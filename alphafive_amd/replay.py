@@ -7,7 +7,8 @@ push() keeps the reference's scalar bookkeeping on the host (one episode at a ti
 and uploads the accepted episode once; push_packed() / iter_push_packed() take the engine's packed DEVICE hand-off buffer
 instead: the host reads its header only and the plies are decoded on the device (no 5-tuples, no per-ply Python, no
 upload); get_data() draws (which positions, quarter turns, flip) on the host and runs the gather + 8-fold symmetry +
-board_to_inputs encoding as one kernel launch.
+board_to_inputs encoding as one kernel launch.  draw_batches() / get_data_device() take those draws to the device too
+(a counter-based generator, specified by draw_reference() below): same distribution, no host work beyond two launches.
 
 Persistence: to_host() reads the ring out as a utils.RandomStack (one af_replay_export: the device writes the records' state
 strings), from_host() / load_records() put records back (af_replay_append_states: the device decodes them), and
@@ -47,6 +48,7 @@ def lib():
         L.af_replay_drop_front.argtypes = [vp, C.c_int32]
         L.af_replay_size.argtypes = [vp]
         L.af_replay_sample.argtypes = [vp, vp, C.c_int32, ip, ip, ip, vp, vp, vp, vp]
+        L.af_replay_sample_device.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]
         L.af_replay_append_packed.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32]
         L.af_replay_set_weights.argtypes = [vp, fp, C.c_int32]
         L.af_replay_check.argtypes = [vp, vp]
@@ -63,6 +65,54 @@ def _check(rc, what):
     if rc < 0:
         raise ReplayError(f"{what}: {lib().af_replay_strerror(rc).decode()} (code {rc})")
     return rc
+
+
+# ---- device-drawn minibatches: the specification af_replay_draw_kernel (csrc/af_replay.hip) is held to, bit for bit ----
+DRAW_TAG = 0x52504C59           # "RPLY": fourth Philox counter word of a replay draw (AF_REPLAY_DRAW_TAG)
+MAX_DRAW = 4096                 # AF_REPLAY_MAX_DRAW: most samples of one minibatch
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """af_philox4x32 of include/af_noise.h on numpy arrays (or scalars) of 32-bit words -> four uint32 arrays.
+    All-zero counter and key -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8."""
+    M = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, np.uint64) & M for c in (c0, c1, c2, c3)])
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2         # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & M, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & M
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def draw_reference(n, num, batches, seed, draw):
+    """Which positions, quarter turns and flips `batches` minibatches of `num` samples take from a buffer of `n` positions
+    -> (idx, turns, flip), each int32[batches][k], k = min(num, n).  This is the specification of the device draw
+    (af_replay_sample_device); it replaces the reference's global-stream draws (utils.py:120,129,136) by a counter-based
+    one with the same distribution.  For minibatch b and logical position i in [0, n), counted from the oldest:
+
+        v        = philox4x32_10(ctr = (i, b, draw mod 2^32, DRAW_TAG), key = (seed mod 2^32, (seed >> 32) mod 2^32))
+        key(i)   = v[0] << 32 | i
+        turns(i) = v[1] >> 30            0..3, np.rot90's k
+        flip(i)  = v[2] >> 31            1 = the vertical flip is applied
+
+    Minibatch b is the k positions with the smallest key, in ascending key order: a uniform k-subset in uniform order, one of
+    the 8 symmetries uniformly and independently per sample.  Positions whose 32-bit words are equal are ordered by the lower
+    index; that favours lower indices by at most n / 2^32 relative (3e-6 at n = 12000)."""
+    n, num, batches = int(n), int(num), int(batches)
+    if n < 0 or num < 0 or batches < 0:
+        raise ValueError("n, num and batches must not be negative")
+    k = min(num, n)
+    seed = int(seed)
+    i = np.arange(n, dtype=np.uint64)[None, :]
+    b = np.arange(batches, dtype=np.uint64)[:, None]
+    v = philox4x32_10(i, b, int(draw), DRAW_TAG, seed, seed >> 32)
+    key = (v[0].astype(np.uint64) << np.uint64(32)) | i                  # distinct for distinct i
+    order = np.argsort(key, axis=1)[:, :k]
+    turns = np.take_along_axis(v[1], order, axis=1) >> np.uint32(30)
+    flip = np.take_along_axis(v[2], order, axis=1) >> np.uint32(31)
+    return order.astype(np.int32), turns.astype(np.int32), flip.astype(np.int32)
 
 
 class _PackedEpisode(object):
@@ -82,8 +132,12 @@ class DeviceRandomStack(utils.RandomStack):
     with to_host() and written with load_records() / from_host().  save() / load() are not the way to the reference's pickles
     here: save_pickles() / load_pickles() are."""
 
-    def __init__(self, board_size, length=2000, device=0, max_episode=None):
+    def __init__(self, board_size, length=2000, device=0, max_episode=None, draw_seed=0):
+        """`draw_seed`: key of the device-drawn minibatches (draw_batches / get_data_device); `draw_counter`, which starts at 0
+        and moves by one per call, is the other half of their address.  Neither touches get_data()."""
         super().__init__(board_size, length)
+        self.draw_seed = int(draw_seed)
+        self.draw_counter = 0
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         # a push may append one episode twice before the eviction brings the size back to `length`
         max_episode = max_episode or board_size * board_size
@@ -267,6 +321,40 @@ class DeviceRandomStack(utils.RandomStack):
                                       flip.ctypes.data_as(ip), boards.data_ptr(), weights.data_ptr(), values.data_ptr(),
                                       policies.data_ptr()), "af_replay_sample")
         return boards, weights, values, policies
+
+    def draw_batches(self, batch_size, batches, return_draws=False):
+        """`batches` independent minibatches of min(batch_size, size) samples, drawn AND gathered on the device (two launches,
+        no host draw, no copy, no wait: af_replay_sample_device): boards[B,num,3,S,S], weights[B,num], values[B,num],
+        policies[B,num,C] as device tensors, with return_draws=True also the int32[3,B,num] tensor of (logical index, quarter
+        turns, flip) per sample.  The draws are draw_reference(size, batch_size, batches, draw_seed, draw_counter) — the
+        reference's distribution (utils.py:118-146), not its global streams; get_data() keeps those.  draw_counter moves by one
+        per call, whatever `batches` is.  An empty stack gives empty tensors without a launch."""
+        S, B = self.board_size, int(batches)
+        if B < 1:
+            raise ValueError("batches must be at least 1")
+        if batch_size > MAX_DRAW:
+            raise ValueError("batch_size %d is more than a device draw holds (%d)" % (batch_size, MAX_DRAW))
+        num = max(0, min(int(batch_size), self._size()))
+        f32 = dict(dtype=torch.float32, device=self.device)
+        boards = torch.empty((B, num, 3, S, S), **f32)
+        weights = torch.empty((B, num), **f32)
+        values = torch.empty((B, num), **f32)
+        policies = torch.empty((B, num, S * S), **f32)
+        draws = torch.empty((3, B, num), dtype=torch.int32, device=self.device) if return_draws else None
+        draw = self.draw_counter & 0xFFFFFFFF
+        self.draw_counter += 1
+        if num > 0:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _check(lib().af_replay_sample_device(self._h, stream, num, B, self.draw_seed & 0xFFFFFFFFFFFFFFFF, draw,
+                                                 boards.data_ptr(), weights.data_ptr(), values.data_ptr(), policies.data_ptr(),
+                                                 draws.data_ptr() if return_draws else None), "af_replay_sample_device")
+        out = (boards, weights, values, policies)
+        return out + (draws,) if return_draws else out
+
+    def get_data_device(self, batch_size=1):
+        """get_data()'s shapes and dtypes from one device-drawn minibatch: draw_batches(batch_size, 1) without the leading
+        dimension."""
+        return tuple(t[0] for t in self.draw_batches(batch_size, 1))
 
     def close(self):
         if getattr(self, "_h", None):

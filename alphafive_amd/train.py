@@ -197,7 +197,7 @@ def _save_buffer(stack, step):
 
 
 def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step=1, resumable=False, ckpt_every=60,
-               weights_on_device=False):
+               weights_on_device=False, device_draws=False):
     """main.py:57-76 with the five gen_data processes replaced by the device batch `engine`
     (alphafive_amd.engine.SelfPlayEngine): every accepted episode triggers 4 minibatches once the buffer is full.
 
@@ -214,7 +214,16 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step
     trainer.device_variables()) snapshots the parameters on the device and the evaluator re-packs them in place
     (af_net_update_device) instead of 42 device-to-host copies, a host re-pack and a reallocation of the evaluator per step.
     `net` may be a network_deep.DeepResNet with a Trainer built on forward_train_deep: its set_variables_device re-packs the
-    bf16 tower in place (af_tower_update_device: launches only)."""
+    bf16 tower in place (af_tower_update_device: launches only).
+
+    device_draws=True takes the minibatch draws off the host too: the four minibatches of an accepted episode come from ONE
+    stack.draw_batches(config.batch_size, 4) (replay.DeviceRandomStack: positions, turns and flips drawn by a counter-based
+    generator on the device, keyed by the stack's draw_seed and draw_counter) and the four steps take its slices — four
+    independent draws from the same buffer state, as the reference's four get_data calls are, but not from its global streams.
+    A stack without draw_batches is a ValueError."""
+    if device_draws and not hasattr(stack, "draw_batches"):
+        raise ValueError("device_draws=True needs a stack with draw_batches (replay.DeviceRandomStack); %s has none" %
+                         type(stack).__name__)
     step = start_step
     on_device = hasattr(stack, "iter_push_packed") and hasattr(engine, "post_episodes_device")
     cap = 256
@@ -227,8 +236,13 @@ def train_loop(config, engine, net, stack, trainer, steps, log=print, start_step
             pushes = (stack.push(data_record, result) for data_record, result in engine.pop_episodes())
         for r in pushes:                                # every finished episode reaches the buffer, also after the last step
             if r and stack.is_full() and step < steps:
+                if device_draws:
+                    drawn = stack.draw_batches(config.batch_size, 4)
                 for i in range(4):                              # (only the last minibatch's scalars are logged: one sync per episode)
-                    boards, weights, values, policies = stack.get_data(batch_size=config.batch_size)
+                    if device_draws:
+                        boards, weights, values, policies = (t[i] for t in drawn)
+                    else:
+                        boards, weights, values, policies = stack.get_data(batch_size=config.batch_size)
                     metrics = trainer.step(boards, weights, values, policies, config.get_lr(step), metrics=i == 3)
                 step += 1
                 if weights_on_device:                           # the engine's evaluator follows the trainer
@@ -253,7 +267,9 @@ def resume(config, net, stack, trainer, log=print):
     """Continue from the newest checkpoint the `checkpoint` file in config.ckpt_path names (main.py:29-34 restore=True): its
     variables go into `trainer` and `net`, the optimiser sidecar into `trainer` if there is one (if not, Adam starts fresh, as
     it does in the reference, whose checkpoints hold no slots), the buffer files of that step into `stack` if they exist.
-    Returns the step to pass to train_loop as `start_step`.  The engine starts from empty boards: see train_loop."""
+    Returns the step to pass to train_loop as `start_step`.  The engine starts from empty boards: see train_loop.
+    The stack's draw_counter (train_loop(device_draws=True)) is not restored either: build the continued run's stack with a
+    `draw_seed` the first run did not use, or it draws the first run's minibatch selections again."""
     prefix = tensorbundle.resolve_checkpoint(config.ckpt_path)
     ckpt_dir, name = os.path.dirname(prefix), os.path.basename(prefix)
     step = int(name.rsplit("-", 1)[1])

@@ -14,6 +14,11 @@
  *           It also owns the codec between its int8 boards and the run-length state strings the reference's records carry
  *           (utils.py:156-196), in both directions: af_replay_export is the way out of the ring (positions in logical order,
  *           as state strings and/or boards, for RandomStack's data*.pkl), af_replay_append_states the way back in.
+ *   device-drawn path — af_replay_sample_device takes the draws of get_data() off the host as well: which positions, turns and
+ *           flips come from a counter-based generator (Philox4x32-10 of af_noise.h, keyed by a seed and a draw counter) in
+ *           af_replay_draw_kernel, which writes the (slot, turns, flip) triples the gather kernel above reads: a training step
+ *           then touches the host for launches only.  Same distribution as the reference's draws, not the same streams: the path
+ *           above stays for whoever needs seeded equality with the reference.
  * Results are bit-identical to the host class (pure gathers of fp32 / small-integer data).
  *
  * Plain pointers, int return codes (0 ok / count, <0 error), no exceptions; one handle per GPU.
@@ -91,6 +96,35 @@ int32_t af_replay_size(const af_replay* r);
  * board with the remapped last action), weights float32[num], values float32[num], policies float32[num][C]. */
 int af_replay_sample(af_replay* r, void* stream, int32_t num, const int32_t* idx, const int32_t* quarter_turns,
                      const int32_t* flip, float* boards_dev, float* weights_dev, float* values_dev, float* policies_dev);
+
+/* Device-drawn get_data: `batches` independent minibatches of `num` samples each, drawn and gathered on the device.
+ * Specification (alphafive_amd/replay.py:draw_reference states it in numpy; the kernel equals it bit for bit): for minibatch b
+ * and logical position i in [0, n), n = af_replay_size, counted from the oldest as in af_replay_sample,
+ *     v        = af_philox4x32(ctr = (i, b, draw, AF_REPLAY_DRAW_TAG), key = ((uint32_t)seed, (uint32_t)(seed >> 32)))   (af_noise.h)
+ *     key(i)   = (uint64_t)v[0] << 32 | i          distinct for distinct i
+ *     turns(i) = v[1] >> 30                        0..3, np.rot90 k
+ *     flip(i)  = v[2] >> 31                        1 = flip applied (the reference's `random.choice([1,2]) == 1`)
+ * and minibatch b is the `num` positions with the smallest key, sample j the j-th smallest: a uniform subset in uniform order
+ * and one of the 8 symmetries uniformly per sample, the distribution of utils.py:120,129,136.  (Equal 32-bit words are ordered by
+ * the lower index: a bias of at most n / 2^32 relative.)  The caller advances `draw` from call to call; one call with
+ * batches = 4 is four independent draws from the same buffer state (main.py:62-68).
+ * Device outputs as af_replay_sample's with a leading [batches]: boards float32[batches][num][3][S][S], weights and values
+ * float32[batches][num], policies float32[batches][num][C]; draws_out_dev (optional, may be NULL) int32[3][batches * num] =
+ * logical index, quarter turns, flip of every sample.
+ * 1 <= num <= AF_REPLAY_MAX_DRAW, num <= af_replay_size (the caller takes the min, as get_data does), 1 <= batches <=
+ * AF_REPLAY_MAX_BATCHES.  A null handle or output and num or batches below 1 are AF_REPLAY_ERR_ARG, anything above its range
+ * AF_REPLAY_ERR_RANGE, both before any HIP call.
+ * Two launches on `stream` and nothing else — af_replay_draw_kernel, one workgroup per minibatch, then af_replay_sample's gather
+ * kernel over batches * num triples: no host staging, no pinned copy, no stream synchronisation (the selection buffer is
+ * reallocated when a call needs a larger one than any before it).  The ring's head, size and capacity travel by value, as in
+ * every call of this header, so a launch is bound to the ring state of the moment it was issued: the call is not meant for
+ * stream capture. */
+#define AF_REPLAY_DRAW_TAG 0x52504C59u   /* "RPLY": the domain of these Philox blocks (fourth counter word) */
+#define AF_REPLAY_MAX_DRAW 4096
+#define AF_REPLAY_MAX_BATCHES 4096
+int af_replay_sample_device(af_replay* r, void* stream, int32_t num, int32_t batches, uint64_t seed, uint32_t draw,
+                            float* boards_dev, float* weights_dev, float* values_dev, float* policies_dev,
+                            int32_t* draws_out_dev);
 
 const char* af_replay_strerror(int code);
 
