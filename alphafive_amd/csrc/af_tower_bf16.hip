@@ -24,7 +24,6 @@
 
 #include <type_traits>
 #include <stdint.h>
-#include <string.h>
 
 #include <vector>
 
@@ -913,17 +912,19 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Device weight packers (af_tower_update_device): fp32 weights in device memory (the layouts the host setters take: OIHW
-// convolutions, [in][out] dense layers) -> every weight-derived buffer of the handle, in place.  They restate, per output
-// element, what the host loops behind af_tower_set_block / _set_stem / _set_heads / _set_dense compute (those loops stay as
-// they are: tests/test_gpu_tower_update.py compares the two byte for byte).  A thread owns one 16-byte fragment row (8 bf16,
-// one vector store) or one fp32 word; the thread index is decoded by div / mod with compile-time region sizes, so every source
-// and destination index is in range by construction for the element counts af_tower_update_device has validated.  No scales,
-// no reductions: nothing here has to come back to the host, which is why the update is launches only.
+// Weight packers, the only ones: fp32 weights in device memory (OIHW convolutions, [in][out] dense layers) -> every
+// weight-derived buffer of the handle, in place.  af_tower_update_device runs them over the caller's device tensors; the host
+// setters (af_tower_set_block / _set_stem / _set_heads / _set_dense) copy their fp32 arrays into the handle's staging area
+// and run them over that, one block or one range of the ends kernel each.  The layout is specified by oracle/tower_pack.py, a
+// numpy restatement tied to the bytes of the former host packers (tests/golden/tower_packed_digests.json);
+// tests/test_gpu_tower_update.py holds both paths to it buffer by buffer.  A thread owns one 16-byte fragment row (8 bf16, one
+// vector store) or one fp32 word; the thread index is decoded by div / mod with compile-time region sizes, so every source and
+// destination index is in range by construction for the element counts the callers have validated or staged.  No scales, no
+// reductions: nothing here has to come back to the host, which is why the update is launches only.
 //
-// pack_bf16: the host bf16_rne in the same integer arithmetic (round to nearest even on the bit pattern: ties both ways, carry
-// into the exponent up to inf, denormals and -0 as they are; NaN keeps its sign and gets a quiet bit).  Not a conversion
-// instruction: the bytes must be the host packer's on every class of input.
+// pack_bf16: round to nearest even on the bit pattern (ties both ways, carry into the exponent up to inf, denormals and -0 as
+// they are; NaN keeps its sign and upper payload and gets a quiet bit).  Not a conversion instruction: the bytes are the
+// specification's on every class of input.
 __device__ __forceinline__ uint32_t pack_bf16(float f) {
     uint32_t u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return ((u >> 16) | 0x40u) & 0xffffu;
@@ -931,7 +932,7 @@ __device__ __forceinline__ uint32_t pack_bf16(float f) {
     return u >> 16;
 }
 __device__ __forceinline__ float pack_bf16_f32(float f) { return __uint_as_float(pack_bf16(f) << 16); }
-__device__ __forceinline__ int pack_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }   // MFMA row -> output (pack_tower)
+__device__ __forceinline__ int pack_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }   // MFMA row -> output: a lane's 16 accumulator rows are 16 consecutive outputs
 __device__ __forceinline__ uint4 pack_row(const uint32_t (&h)[8]) {
     return uint4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
 }
@@ -977,10 +978,14 @@ __global__ __launch_bounds__(256) void af_tower_pack_blocks_kernel(PackBlocksArg
     if (r < 128) A.b2[b][r] = A.src[b][3][r] + A.src[b][5][r];
 }
 
-// stem, the heads' 1x1 convolutions and the dense layers: one launch, the thread index walks the regions below in order
+// stem, the heads' 1x1 convolutions and the dense layers: the thread index r walks the regions below in order, stem in
+// [0, kPackEndsStem), heads up to kPackEndsHeads, the dense layers in the rest.  A launch covers [first, end): all of it for
+// af_tower_update_device, one group's range for a host setter, which leaves the other groups' pointers null (never reached).
 constexpr int kRowsStem = 4 * 8 * 64, kRowsHeadsA = 8 * 64, kRowsWp = 121 * 4 * 64, kRowsWv = 31 * 2 * 64;
-constexpr int kPackEndsThreads = kRowsStem + 128 + 20 * 128 + 20 + kRowsHeadsA + 32 + kRowsWp + kRowsWv + 121 + 64 + 64 + 1;
+constexpr int kPackEndsStem = kRowsStem + 128, kPackEndsHeads = kPackEndsStem + 20 * 128 + 20 + kRowsHeadsA + 32;
+constexpr int kPackEndsThreads = kPackEndsHeads + kRowsWp + kRowsWv + 121 + 64 + 64 + 1;
 struct PackEndsArgs {
+    int first, end;
     const float *stem_w, *stem_b, *vconv_w, *vconv_b, *pconv_w, *pconv_b, *vfc1_w, *vfc1_b, *vfc2_w, *vfc2_b, *pfc_w, *pfc_b;
     uint4* o_stem_w;
     float* o_stem_b;
@@ -992,7 +997,8 @@ struct PackEndsArgs {
 };
 
 __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A) {
-    int r = (int)(blockIdx.x * 256 + threadIdx.x);
+    int r = A.first + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (r >= A.end) return;
     if (r < kRowsStem) {                         // [wave][k-step][lane]: group g = 2 s + (lane >> 5) = (cin, ky), 5 taps + 3 zeros; g = 15 is zero
         const int lane = r & 63, s = (r >> 6) & 7, wv = r >> 9;                   // wv < 4
         const int co = 32 * wv + pack_perm(lane & 31), g = 2 * s + (lane >> 5);
@@ -1054,7 +1060,7 @@ __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A)
         return;
     }
     r -= kRowsWv;
-    if (r < 121) { A.o_dense_pb[r] = pack_bf16_f32(A.pfc_b[r]); return; }        // (words 121..127 keep the -1e30 af_tower_set_dense wrote)
+    if (r < 121) { A.o_dense_pb[r] = pack_bf16_f32(A.pfc_b[r]); return; }        // (words 121..127 keep the -1e30 af_tower_create wrote)
     r -= 121;
     if (r < 64) { A.o_dense_vb1[r] = pack_bf16_f32(A.vfc1_b[r]); return; }
     r -= 64;
@@ -1064,62 +1070,103 @@ __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A)
 }
 
 // ------------------------------------------------------------------ host ------------------------------------------------------------------
+// The handle's weight-derived buffers, in af_tower_debug_weights' order: the four of every block, then the twelve of the ends.
+enum { kW1, kW2, kB1, kB2 };        // w1 / w2: A fragments of a block's two convolutions [wave][s][lane][e], s = 8 tap + cin / 16, then the 1x1 projection
+enum { kStemW, kStemB, kHeadsW, kHeadsB, kHeadsA, kHeadsB32, kDenseWp, kDenseWv, kDensePb, kDenseVb1, kDenseVw2, kDenseVb2, kEnds };
+
+static int64_t buffer_bytes(int i, int blocks) {
+    static const int64_t kBlock[4] = {(int64_t)kRowsW1 * 16, (int64_t)kRowsW2 * 16, 128 * 4, 128 * 4};
+    static const int64_t kEnd[kEnds] = {(int64_t)kRowsStem * 16, 128 * 4, 20 * 128 * 4, 20 * 4, (int64_t)kRowsHeadsA * 16, 32 * 4,
+                                        (int64_t)kRowsWp * 16, (int64_t)kRowsWv * 16, 128 * 4, 64 * 4, 64 * 4, 4};
+    return i < 4 * blocks ? kBlock[i % 4] : kEnd[i - 4 * blocks];
+}
+
+// A group is what one host setter fills: block b is group b, then stem, heads and dense.
+enum { kStem, kHeads, kDense, kEndGroups };
+static int group_of(int i, int blocks) {
+    if (i < 4 * blocks) return i / 4;
+    const int e = i - 4 * blocks;
+    return blocks + (e < kHeadsW ? kStem : e < kDenseWp ? kHeads : kDense);
+}
+
+// element counts of af_tower_update_device's tensors, in its order (include/af_tower_bf16.h); a host setter takes a run of them
+static int64_t update_count(int i, int blocks) {
+    static const int64_t kBlock[6] = {147456, 128, 147456, 128, 16384, 128};
+    static const int64_t kTail[10] = {512, 4, 2048, 16, 30976, 64, 64, 1, 234256, 121};
+    if (i == 0) return 9600;
+    if (i == 1) return 128;
+    if (i < 2 + 6 * blocks) return kBlock[(i - 2) % 6];
+    return kTail[i - 2 - 6 * blocks];
+}
+
+constexpr int64_t kStageFloats = 2 * 147456 + 16384 + 3 * 128;      // the largest setter's tensors, a block's six: 1.25 MB
+constexpr int64_t kDumpBytes = 4096;                                // TowerArgs::dump
+
 struct af_tower {
     int S = 0, width = 0, blocks = 0, device = 0;
-    std::vector<uint4*> w1, w2;             // A fragments of a block's two convolutions (pack_tower)
-    std::vector<float*> b1, b2;
-    std::vector<char> set;
-    uint4* stem_w = nullptr;
+    char* arena = nullptr;          // the one allocation: every buffer of the table, the staging area and dump, at 256-byte offsets
+    std::vector<char*> buf;         // 4 * blocks + 12 buffers; their addresses never change
+    std::vector<char> set;          // per group: its host setter has run
+    float* stage = nullptr;         // where a host setter's fp32 arrays wait for the packers
     char* dump = nullptr;
-    float* stem_b = nullptr;
-    float* heads_w = nullptr;
-    float* heads_b = nullptr;
-    uint4* heads_a = nullptr;     // af_tower_heads_mfma_kernel: A fragments
-    float* heads_b32 = nullptr;   // ... and its 32 biases
-    uint4 *dense_wp = nullptr, *dense_wv = nullptr;     // af_tower_dense_kernel: packed policy / value fc1 weights
-    float *dense_pb = nullptr, *dense_vb1 = nullptr, *dense_vw2 = nullptr, *dense_vb2 = nullptr;
+    template <class T> T* block(int b, int k) const { return reinterpret_cast<T*>(buf[4 * b + k]); }
+    template <class T> T* end(int k) const { return reinterpret_cast<T*>(buf[4 * blocks + k]); }
 };
 
-static uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
+static bool all_set(const af_tower* t) {
+    for (char c : t->set) if (!c) return false;
+    return true;
 }
 
-static float bf16_round(float f) {
-    const uint32_t u = (uint32_t)bf16_rne(f) << 16;
-    float r;
-    memcpy(&r, &u, 4);
-    return r;
+// blocks b0 .. b0 + nb - 1 (nb <= kPackBlocks) from src: six device tensors per block, af_tower_update_device's order
+static void pack_blocks(const af_tower* t, hipStream_t st, int b0, int nb, const float* const* src) {
+    PackBlocksArgs a = {};
+    for (int j = 0; j < nb; ++j) {
+        for (int k = 0; k < 6; ++k) a.src[j][k] = src[6 * j + k];
+        a.w1[j] = t->block<uint4>(b0 + j, kW1); a.w2[j] = t->block<uint4>(b0 + j, kW2);
+        a.b1[j] = t->block<float>(b0 + j, kB1); a.b2[j] = t->block<float>(b0 + j, kB2);
+    }
+    hipLaunchKernelGGL(af_tower_pack_blocks_kernel, dim3(kPackBlockThreads / 256, nb), dim3(256), 0, st, a);
 }
 
-// A fragments: [wave][s][lane][e] = W[cout = 32*wave + perm(lane&31)][cin = 16*cc + 8*(lane>>5) + e][tap t], s = 8*t + cc;
-// s = 72 + cc: the 1x1 projection.
-static std::vector<uint16_t> pack_tower(const float* w3, const float* w1x1) {
-    const int NS = w1x1 ? 80 : 72;
-    std::vector<uint16_t> out((size_t)4 * NS * 64 * 8);
-    for (int wv = 0; wv < 4; ++wv)
-        for (int s = 0; s < NS; ++s)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int m = lane & 31;                                    // MFMA row -> cout: lane half kg = (m>>2)&1 ends up holding
-                    const int co = 32 * wv + 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3);   // 16 consecutive couts in its 16 C rows
-                    const int cc = s < 72 ? s % 8 : s - 72;
-                    const int ci = 16 * cc + 8 * (lane >> 5) + e;
-                    const float v = s < 72 ? w3[((size_t)co * 128 + ci) * 9 + s / 8] : w1x1[(size_t)co * 128 + ci];
-                    out[(((size_t)wv * NS + s) * 64 + lane) * 8 + e] = bf16_rne(v);
-                }
-    return out;
+// range [first, end) of the ends kernel from src: stem_w, stem_b, then the ten device tensors behind the blocks in
+// af_tower_update_device's order; the entries of a group the range stays out of may be null
+static void pack_ends(const af_tower* t, hipStream_t st, const float* const* src, int first, int end) {
+    PackEndsArgs a;
+    a.first = first; a.end = end;
+    a.stem_w = src[0]; a.stem_b = src[1]; a.vconv_w = src[2]; a.vconv_b = src[3]; a.pconv_w = src[4]; a.pconv_b = src[5];
+    a.vfc1_w = src[6]; a.vfc1_b = src[7]; a.vfc2_w = src[8]; a.vfc2_b = src[9]; a.pfc_w = src[10]; a.pfc_b = src[11];
+    a.o_stem_w = t->end<uint4>(kStemW); a.o_stem_b = t->end<float>(kStemB);
+    a.o_heads_w = t->end<float>(kHeadsW); a.o_heads_b = t->end<float>(kHeadsB);
+    a.o_heads_a = t->end<uint4>(kHeadsA); a.o_heads_b32 = t->end<float>(kHeadsB32);
+    a.o_dense_wp = t->end<uint4>(kDenseWp); a.o_dense_wv = t->end<uint4>(kDenseWv); a.o_dense_pb = t->end<float>(kDensePb);
+    a.o_dense_vb1 = t->end<float>(kDenseVb1); a.o_dense_vw2 = t->end<float>(kDenseVw2); a.o_dense_vb2 = t->end<float>(kDenseVb2);
+    hipLaunchKernelGGL(af_tower_pack_ends_kernel, dim3((end - first + 255) / 256), dim3(256), 0, st, a);
 }
 
-template <class T>
-static int upload(T** dst, const void* src, size_t bytes) {
-    if (*dst) (void)hipFree(*dst);
-    *dst = nullptr;
-    TW_HIP_OK(hipMalloc(reinterpret_cast<void**>(dst), bytes));
-    TW_HIP_OK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+// A host setter, first half: wait for the device (forwards in flight read the buffers), then copy the caller's n fp32 arrays —
+// entries first .. first + n - 1 of af_tower_update_device's table, with its counts — into the staging area as they are.
+// dev[k]: where array k landed (256-byte aligned).
+static int stage(af_tower* t, int first, int n, const float* const* host, const float** dev) {
+    TW_HIP_OK(hipSetDevice(t->device));
+    TW_HIP_OK(hipDeviceSynchronize());
+    int64_t at = 0;
+    for (int k = 0; k < n; ++k) {
+        const int64_t count = update_count(first + k, t->blocks);
+        if (at + count > kStageFloats) return AF_TOWER_ERR_ARG;         // (no setter's arrays are larger than a block's)
+        TW_HIP_OK(hipMemcpy(t->stage + at, host[k], (size_t)count * 4, hipMemcpyHostToDevice));
+        dev[k] = t->stage + at;
+        at += (count + 63) & ~(int64_t)63;
+    }
+    return AF_TOWER_OK;
+}
+
+// ... and second half, behind the packer's launch on the null stream: when this returns the weights are in place and both the
+// caller's arrays and the staging area are free again
+static int packed(af_tower* t, int group) {
+    TW_HIP_OK(hipGetLastError());
+    TW_HIP_OK(hipDeviceSynchronize());
+    t->set[group] = 1;
     return AF_TOWER_OK;
 }
 
@@ -1153,20 +1200,35 @@ const char* af_tower_strerror(int code) {
     }
 }
 
-int af_tower_create(int32_t S, int32_t width, int32_t blocks, int32_t device, af_tower** out) {
-    if (!out || S != kS || width != 128 || blocks < 1) return AF_TOWER_ERR_ARG;
-    TW_HIP_OK(hipSetDevice(device));
-    af_tower* t = new af_tower();
-    t->S = S; t->width = width; t->blocks = blocks; t->device = device;
-    t->w1.assign(blocks, nullptr); t->w2.assign(blocks, nullptr);
-    t->b1.assign(blocks, nullptr); t->b2.assign(blocks, nullptr);
-    t->set.assign(blocks, 0);
+static int allocate(af_tower* t) {
+    TW_HIP_OK(hipSetDevice(t->device));
 #define TW_ATTR(P, D) TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv<P, D>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
     TW_ATTR(false, 8); TW_ATTR(true, 8); TW_ATTR(false, 12); TW_ATTR(true, 12); TW_ATTR(false, 16); TW_ATTR(true, 16);
 #undef TW_ATTR
     TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv3<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv3<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    { void* q = nullptr; TW_HIP_OK(hipMalloc(&q, 4096)); t->dump = static_cast<char*>(q); }
+    const int n = 4 * t->blocks + kEnds;
+    auto padded = [](int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); };
+    size_t total = padded(kStageFloats * 4) + padded(kDumpBytes);
+    for (int i = 0; i < n; ++i) total += padded(buffer_bytes(i, t->blocks));
+    { void* q = nullptr; TW_HIP_OK(hipMalloc(&q, total)); t->arena = static_cast<char*>(q); }
+    char* p = t->arena;
+    for (int i = 0; i < n; ++i) { t->buf.push_back(p); p += padded(buffer_bytes(i, t->blocks)); }
+    t->stage = reinterpret_cast<float*>(p); p += padded(kStageFloats * 4);
+    t->dump = p;
+    t->set.assign(t->blocks + kEndGroups, 0);
+    // dense_pb's words 121..127 — policy outputs that do not exist — are -1e30 for good: no packer writes them
+    const float tail[7] = {-1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f};
+    TW_HIP_OK(hipMemcpy(t->end<float>(kDensePb) + 121, tail, sizeof(tail), hipMemcpyHostToDevice));
+    return AF_TOWER_OK;
+}
+
+int af_tower_create(int32_t S, int32_t width, int32_t blocks, int32_t device, af_tower** out) {
+    if (!out || S != kS || width != 128 || blocks < 1) return AF_TOWER_ERR_ARG;
+    af_tower* t = new af_tower();
+    t->S = S; t->width = width; t->blocks = blocks; t->device = device;
+    const int rc = allocate(t);
+    if (rc) { af_tower_destroy(t); return rc; }
     *out = t;
     return AF_TOWER_OK;
 }
@@ -1174,128 +1236,61 @@ int af_tower_create(int32_t S, int32_t width, int32_t blocks, int32_t device, af
 void af_tower_destroy(af_tower* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    for (auto p : t->w1) if (p) (void)hipFree(p);
-    for (auto p : t->w2) if (p) (void)hipFree(p);
-    for (auto p : t->b1) if (p) (void)hipFree(p);
-    for (auto p : t->b2) if (p) (void)hipFree(p);
-    if (t->stem_w) (void)hipFree(t->stem_w);
-    if (t->dump) (void)hipFree(t->dump);
-    if (t->stem_b) (void)hipFree(t->stem_b);
-    if (t->heads_w) (void)hipFree(t->heads_w);
-    if (t->heads_b) (void)hipFree(t->heads_b);
-    if (t->heads_a) (void)hipFree(t->heads_a);
-    if (t->heads_b32) (void)hipFree(t->heads_b32);
-    if (t->dense_wp) (void)hipFree(t->dense_wp);
-    if (t->dense_wv) (void)hipFree(t->dense_wv);
-    if (t->dense_pb) (void)hipFree(t->dense_pb);
-    if (t->dense_vb1) (void)hipFree(t->dense_vb1);
-    if (t->dense_vw2) (void)hipFree(t->dense_vw2);
-    if (t->dense_vb2) (void)hipFree(t->dense_vb2);
+    if (t->arena) (void)hipFree(t->arena);
     delete t;
 }
 
 int af_tower_set_block(af_tower* t, int32_t b, const float* c1_w, const float* c1_b, const float* c2_w, const float* c2_b,
                        const float* res_w, const float* res_b) {
     if (!t || b < 0 || b >= t->blocks || !c1_w || !c1_b || !c2_w || !c2_b || !res_w || !res_b) return AF_TOWER_ERR_ARG;
-    TW_HIP_OK(hipSetDevice(t->device));
-    const std::vector<uint16_t> p1 = pack_tower(c1_w, nullptr), p2 = pack_tower(c2_w, res_w);
-    std::vector<float> bb(128);
-    int rc = upload(&t->w1[b], p1.data(), p1.size() * 2);
-    if (!rc) rc = upload(&t->w2[b], p2.data(), p2.size() * 2);
-    if (!rc) rc = upload(&t->b1[b], c1_b, 128 * 4);
-    for (int i = 0; i < 128; ++i) bb[i] = c2_b[i] + res_b[i];
-    if (!rc) rc = upload(&t->b2[b], bb.data(), 128 * 4);
-    if (!rc) t->set[b] = 1;
-    return rc;
+    const float* const host[6] = {c1_w, c1_b, c2_w, c2_b, res_w, res_b};
+    const float* dev[6];
+    const int rc = stage(t, 2 + 6 * b, 6, host, dev);
+    if (rc) return rc;
+    pack_blocks(t, nullptr, b, 1, dev);
+    return packed(t, b);
 }
-
 
 int af_tower_set_stem(af_tower* t, const float* w, const float* b) {
     if (!t || !w || !b) return AF_TOWER_ERR_ARG;
-    TW_HIP_OK(hipSetDevice(t->device));
-    std::vector<uint16_t> pk((size_t)4 * 8 * 64 * 8, 0);                 // [wave][s][lane][e]
-    for (int wv = 0; wv < 4; ++wv)
-        for (int s = 0; s < 8; ++s)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int m = lane & 31, g = 2 * s + (lane >> 5);
-                const int co = 32 * wv + 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3);
-                if (g >= 15) continue;
-                for (int e = 0; e < 5; ++e)                               // w OIHW [128][3][5][5]
-                    pk[(((size_t)wv * 8 + s) * 64 + lane) * 8 + e] = bf16_rne(w[(((size_t)co * 3 + g / 5) * 5 + g % 5) * 5 + e]);
-            }
-    int rc = upload(&t->stem_w, pk.data(), pk.size() * 2);
-    if (!rc) rc = upload(&t->stem_b, b, 128 * 4);
-    return rc;
+    const float* const host[2] = {w, b};
+    const float* dev[12] = {};
+    const int rc = stage(t, 0, 2, host, dev);
+    if (rc) return rc;
+    pack_ends(t, nullptr, dev, 0, kPackEndsStem);
+    return packed(t, t->blocks + kStem);
 }
 
 int af_tower_set_heads(af_tower* t, const float* vconv_w, const float* vconv_b, const float* pconv_w, const float* pconv_b) {
     if (!t || !vconv_w || !vconv_b || !pconv_w || !pconv_b) return AF_TOWER_ERR_ARG;
-    TW_HIP_OK(hipSetDevice(t->device));
-    std::vector<float> w(20 * 128), b(20);
-    for (int c = 0; c < 20; ++c) {
-        b[c] = c < 4 ? vconv_b[c] : pconv_b[c - 4];
-        for (int k = 0; k < 128; ++k) w[c * 128 + k] = bf16_round(c < 4 ? vconv_w[c * 128 + k] : pconv_w[(c - 4) * 128 + k]);
-    }
-    int rc = upload(&t->heads_w, w.data(), w.size() * 4);
-    if (!rc) rc = upload(&t->heads_b, b.data(), b.size() * 4);
-    // A fragments of the MFMA kernel: [k-step][lane][e] = W[o = perm(lane & 31)][ch = 16 step + 8 (lane >> 5) + e] (same row permutation
-    // as pack_tower: a lane's accumulator rows are 16 consecutive outputs)
-    auto perm = [](int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); };
-    std::vector<uint16_t> a((size_t)8 * 64 * 8, 0);
-    for (int step = 0; step < 8; ++step)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 8; ++e) {
-                const int o = perm(lane & 31), ch = 16 * step + 8 * (lane >> 5) + e;
-                if (o < 20) a[((size_t)step * 64 + lane) * 8 + e] = bf16_rne(w[o * 128 + ch]);
-            }
-    std::vector<float> b32(32, 0.0f);
-    for (int o = 0; o < 20; ++o) b32[o] = b[o];
-    if (!rc) rc = upload(&t->heads_a, a.data(), a.size() * 2);
-    if (!rc) rc = upload(&t->heads_b32, b32.data(), b32.size() * 4);
-    return rc;
+    const float* const host[4] = {vconv_w, vconv_b, pconv_w, pconv_b};
+    const float* dev[12] = {};
+    const int rc = stage(t, 2 + 6 * t->blocks, 4, host, dev + 2);
+    if (rc) return rc;
+    pack_ends(t, nullptr, dev, kPackEndsStem, kPackEndsHeads);
+    return packed(t, t->blocks + kHeads);
 }
 
 // dense layers (network.py:73-76,85): vfc1 [484][64] + [64], vfc2 [64] + [1], pfc [1936][121] + [121], all [in][out] fp32
 int af_tower_set_dense(af_tower* t, const float* vfc1_w, const float* vfc1_b, const float* vfc2_w, const float* vfc2_b,
                        const float* pfc_w, const float* pfc_b) {
     if (!t || !vfc1_w || !vfc1_b || !vfc2_w || !vfc2_b || !pfc_w || !pfc_b) return AF_TOWER_ERR_ARG;
-    TW_HIP_OK(hipSetDevice(t->device));
-    auto perm = [](int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); };
-    std::vector<uint16_t> wp((size_t)121 * 4 * 64 * 8, 0), wv((size_t)31 * 2 * 64 * 8, 0);
-    for (int k = 0; k < 121; ++k)
-        for (int tile = 0; tile < 4; ++tile)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int o = 32 * tile + perm(lane & 31), ki = 16 * k + 8 * (lane >> 5) + e;
-                    if (o < 121) wp[((((size_t)k * 4 + tile) * 64) + lane) * 8 + e] = bf16_rne(pfc_w[(size_t)ki * 121 + o]);
-                }
-    for (int k = 0; k < 31; ++k)
-        for (int tile = 0; tile < 2; ++tile)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int o = 32 * tile + perm(lane & 31), ki = 16 * k + 8 * (lane >> 5) + e;
-                    if (ki < 484) wv[((((size_t)k * 2 + tile) * 64) + lane) * 8 + e] = bf16_rne(vfc1_w[(size_t)ki * 64 + o]);
-                }
-    std::vector<float> pb(128, -1.0e30f), vb1(vfc1_b, vfc1_b + 64), vw2(64);
-    for (int o = 0; o < 121; ++o) pb[o] = bf16_round(pfc_b[o]);
-    for (int o = 0; o < 64; ++o) { vb1[o] = bf16_round(vfc1_b[o]); vw2[o] = bf16_round(vfc2_w[o]); }
-    const float vb2 = bf16_round(vfc2_b[0]);
-    int rc = upload(&t->dense_wp, wp.data(), wp.size() * 2);
-    if (!rc) rc = upload(&t->dense_wv, wv.data(), wv.size() * 2);
-    if (!rc) rc = upload(&t->dense_pb, pb.data(), pb.size() * 4);
-    if (!rc) rc = upload(&t->dense_vb1, vb1.data(), vb1.size() * 4);
-    if (!rc) rc = upload(&t->dense_vw2, vw2.data(), vw2.size() * 4);
-    if (!rc) rc = upload(&t->dense_vb2, &vb2, 4);
-    return rc;
+    const float* const host[6] = {vfc1_w, vfc1_b, vfc2_w, vfc2_b, pfc_w, pfc_b};
+    const float* dev[12] = {};
+    const int rc = stage(t, 2 + 6 * t->blocks + 4, 6, host, dev + 6);
+    if (rc) return rc;
+    pack_ends(t, nullptr, dev, kPackEndsHeads, kPackEndsThreads);
+    return packed(t, t->blocks + kDense);
 }
 
 int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* pin_dev, float* policy_dev, float* value_dev,
                    int32_t batch) {
     if (!t || !vin_dev || !pin_dev || !policy_dev || !value_dev || batch < 1) return AF_TOWER_ERR_ARG;
-    if (!t->dense_wp || !t->dense_vb2) return AF_TOWER_ERR_STATE;
+    if (!t->set[t->blocks + kDense]) return AF_TOWER_ERR_STATE;
     DenseArgs a;
     a.vin = static_cast<const __bf16*>(vin_dev); a.pin = static_cast<const __bf16*>(pin_dev);
-    a.wp = t->dense_wp; a.wv = t->dense_wv; a.pb = t->dense_pb; a.vb1 = t->dense_vb1; a.vw2 = t->dense_vw2; a.vb2 = t->dense_vb2;
+    a.wp = t->end<uint4>(kDenseWp); a.wv = t->end<uint4>(kDenseWv); a.pb = t->end<float>(kDensePb);
+    a.vb1 = t->end<float>(kDenseVb1); a.vw2 = t->end<float>(kDenseVw2); a.vb2 = t->end<float>(kDenseVb2);
     a.policy = policy_dev; a.value = value_dev; a.batch = batch;
     const int blocks = (batch + 31) / 32;
     hipLaunchKernelGGL(af_tower_dense_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, static_cast<hipStream_t>(stream), a);
@@ -1305,9 +1300,9 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
 
 int af_tower_stem(af_tower* t, void* stream, const float* planes_dev, void* x_dev, int32_t batch) {
     if (!t || !planes_dev || !x_dev || batch < 1) return AF_TOWER_ERR_ARG;
-    if (!t->stem_w) return AF_TOWER_ERR_STATE;
+    if (!t->set[t->blocks + kStem]) return AF_TOWER_ERR_STATE;
     StemArgs a;
-    a.planes = planes_dev; a.w = t->stem_w; a.bias = t->stem_b; a.out = static_cast<char*>(x_dev); a.batch = batch;
+    a.planes = planes_dev; a.w = t->end<uint4>(kStemW); a.bias = t->end<float>(kStemB); a.out = static_cast<char*>(x_dev); a.batch = batch;
     const int grid = batch < 1024 ? batch : 1024;
     hipLaunchKernelGGL(af_tower_stem_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     TW_HIP_OK(hipGetLastError());
@@ -1316,16 +1311,16 @@ int af_tower_stem(af_tower* t, void* stream, const float* planes_dev, void* x_de
 
 int af_tower_heads(af_tower* t, void* stream, const void* x_dev, void* vin_dev, void* pin_dev, int32_t batch) {
     if (!t || !x_dev || !vin_dev || !pin_dev || batch < 1) return AF_TOWER_ERR_ARG;
-    if (!t->heads_w) return AF_TOWER_ERR_STATE;
+    if (!t->set[t->blocks + kHeads]) return AF_TOWER_ERR_STATE;
     HeadsArgs a;
-    a.x = static_cast<const char*>(x_dev); a.w = t->heads_w; a.b = t->heads_b;
+    a.x = static_cast<const char*>(x_dev); a.w = t->end<float>(kHeadsW); a.b = t->end<float>(kHeadsB);
     a.vin = static_cast<__bf16*>(vin_dev); a.pin = static_cast<__bf16*>(pin_dev); a.batch = batch;
     const int grid = batch < 2048 ? batch : 2048;
     if (g_heads == 0) {
         hipLaunchKernelGGL(af_tower_heads_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     } else {
         HeadsMfmaArgs m;
-        m.x = a.x; m.a = t->heads_a; m.b = t->heads_b32; m.vin = a.vin; m.pin = a.pin; m.batch = batch;
+        m.x = a.x; m.a = t->end<uint4>(kHeadsA); m.b = t->end<float>(kHeadsB32); m.vin = a.vin; m.pin = a.pin; m.batch = batch;
         hipLaunchKernelGGL(af_tower_heads_mfma_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), m);
     }
     TW_HIP_OK(hipGetLastError());
@@ -1337,7 +1332,7 @@ int64_t af_tower_plane_elems(const af_tower*) { return (int64_t)128 * kPIX; }
 
 int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch) {
     if (!t || !x_dev || !g_dev || batch < 1) return AF_TOWER_ERR_ARG;
-    for (char c : t->set) if (!c) return AF_TOWER_ERR_STATE;
+    for (int b = 0; b < t->blocks; ++b) if (!t->set[b]) return AF_TOWER_ERR_STATE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int dev = 0, ncu = 256;
     TW_HIP_OK(hipGetDevice(&dev));
@@ -1348,13 +1343,13 @@ int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_
         TowerArgs a;
         a.batch = batch; a.abl = g_abl; a.dump = t->dump;
         const char* xin = static_cast<const char*>(x_dev);
-        a.in = xin; a.in2 = nullptr; a.w = t->w1[b]; a.bias = t->b1[b]; a.out = static_cast<char*>(g_dev);
+        a.in = xin; a.in2 = nullptr; a.w = t->block<uint4>(b, kW1); a.bias = t->block<float>(b, kB1); a.out = static_cast<char*>(g_dev);
         // ring depth per kernel: the deepest that hipcc allocates without scratch (a scratch reload's vmcnt(0) would
         // also wait for the LDS-DMA of the next position: measured 400 vs 230 us per launch)
         const int d1 = g_depth ? g_depth : 12, d2 = g_depth ? g_depth : 8;
         if (g_engine == 2 || g_engine == 3) {     // r4: epilogue overlapped with the other tile pair's MFMAs (3: first convolution only)
             hipLaunchKernelGGL((af_tower_conv3<false, 8>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-            a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->w2[b]; a.bias = t->b2[b];
+            a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->block<uint4>(b, kW2); a.bias = t->block<float>(b, kB2);
             a.out = static_cast<char*>(x_dev);
             if (g_engine == 2) hipLaunchKernelGGL((af_tower_conv3<true, 8>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
             else hipLaunchKernelGGL((af_tower_conv<true, 8>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
@@ -1363,7 +1358,7 @@ int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_
         if (d1 == 16) hipLaunchKernelGGL((af_tower_conv<false, 16>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
         else if (d1 == 12) hipLaunchKernelGGL((af_tower_conv<false, 12>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
         else hipLaunchKernelGGL((af_tower_conv<false, 8>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-        a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->w2[b]; a.bias = t->b2[b];
+        a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->block<uint4>(b, kW2); a.bias = t->block<float>(b, kB2);
         a.out = static_cast<char*>(x_dev);
         if (d2 == 16) hipLaunchKernelGGL((af_tower_conv<true, 16>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
         else if (d2 == 12) hipLaunchKernelGGL((af_tower_conv<true, 12>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
@@ -1382,73 +1377,31 @@ int af_tower_debug_cycles(unsigned long long* host) {
 #endif
 
 // ---- weights without the host ----
-// element counts of af_tower_update_device's tensors, in its order (include/af_tower_bf16.h)
-static int64_t update_count(int i, int blocks) {
-    static const int64_t kBlock[6] = {147456, 128, 147456, 128, 16384, 128};
-    static const int64_t kTail[10] = {512, 4, 2048, 16, 30976, 64, 64, 1, 234256, 121};
-    if (i == 0) return 9600;
-    if (i == 1) return 128;
-    if (i < 2 + 6 * blocks) return kBlock[(i - 2) % 6];
-    return kTail[i - 2 - 6 * blocks];
-}
-
-static bool all_set(const af_tower* t) {
-    for (char c : t->set) if (!c) return false;
-    return t->stem_w && t->stem_b && t->heads_w && t->heads_b && t->heads_a && t->heads_b32 && t->dense_wp && t->dense_wv &&
-           t->dense_pb && t->dense_vb1 && t->dense_vw2 && t->dense_vb2;
-}
-
 int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_ptrs, const int64_t* counts, int32_t n) {
     // all or nothing: everything is checked before the first launch
     if (!t || !dev_ptrs || !counts || n != 12 + 6 * t->blocks) return AF_TOWER_ERR_ARG;
     for (int i = 0; i < n; ++i)
         if (!dev_ptrs[i] || counts[i] != update_count(i, t->blocks)) return AF_TOWER_ERR_ARG;
-    if (!all_set(t)) return AF_TOWER_ERR_STATE;                  // the host setters allocate the buffers: nothing to write into yet
+    if (!all_set(t)) return AF_TOWER_ERR_STATE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int b0 = 0; b0 < t->blocks; b0 += kPackBlocks) {
-        const int nb = t->blocks - b0 < kPackBlocks ? t->blocks - b0 : kPackBlocks;
-        PackBlocksArgs a = {};
-        for (int j = 0; j < nb; ++j) {
-            for (int k = 0; k < 6; ++k) a.src[j][k] = dev_ptrs[2 + 6 * (b0 + j) + k];
-            a.w1[j] = t->w1[b0 + j]; a.w2[j] = t->w2[b0 + j]; a.b1[j] = t->b1[b0 + j]; a.b2[j] = t->b2[b0 + j];
-        }
-        hipLaunchKernelGGL(af_tower_pack_blocks_kernel, dim3(kPackBlockThreads / 256, nb), dim3(256), 0, st, a);
-    }
-    const float* const* e = dev_ptrs + 2 + 6 * t->blocks;
-    PackEndsArgs a;
-    a.stem_w = dev_ptrs[0]; a.stem_b = dev_ptrs[1];
-    a.vconv_w = e[0]; a.vconv_b = e[1]; a.pconv_w = e[2]; a.pconv_b = e[3];
-    a.vfc1_w = e[4]; a.vfc1_b = e[5]; a.vfc2_w = e[6]; a.vfc2_b = e[7]; a.pfc_w = e[8]; a.pfc_b = e[9];
-    a.o_stem_w = t->stem_w; a.o_stem_b = t->stem_b; a.o_heads_w = t->heads_w; a.o_heads_b = t->heads_b;
-    a.o_heads_a = t->heads_a; a.o_heads_b32 = t->heads_b32; a.o_dense_wp = t->dense_wp; a.o_dense_wv = t->dense_wv;
-    a.o_dense_pb = t->dense_pb; a.o_dense_vb1 = t->dense_vb1; a.o_dense_vw2 = t->dense_vw2; a.o_dense_vb2 = t->dense_vb2;
-    hipLaunchKernelGGL(af_tower_pack_ends_kernel, dim3((kPackEndsThreads + 255) / 256), dim3(256), 0, st, a);
+    for (int b0 = 0; b0 < t->blocks; b0 += kPackBlocks)
+        pack_blocks(t, st, b0, t->blocks - b0 < kPackBlocks ? t->blocks - b0 : kPackBlocks, dev_ptrs + 2 + 6 * b0);
+    const float* ends[12] = {dev_ptrs[0], dev_ptrs[1]};
+    for (int k = 0; k < 10; ++k) ends[2 + k] = dev_ptrs[2 + 6 * t->blocks + k];
+    pack_ends(t, st, ends, 0, kPackEndsThreads);
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
 
 int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes) {
-    if (!t || index < 0 || index >= 4 * t->blocks + 12) return AF_TOWER_ERR_ARG;
-    const void* p = nullptr;
-    int64_t bytes = 0;
-    if (index < 4 * t->blocks) {
-        const int b = index / 4;
-        const void* const ptr[4] = {t->w1[b], t->w2[b], t->b1[b], t->b2[b]};
-        const int64_t size[4] = {(int64_t)kRowsW1 * 16, (int64_t)kRowsW2 * 16, 128 * 4, 128 * 4};
-        p = ptr[index % 4]; bytes = size[index % 4];
-    } else {
-        const void* const ptr[12] = {t->stem_w, t->stem_b, t->heads_w, t->heads_b, t->heads_a, t->heads_b32,
-                                     t->dense_wp, t->dense_wv, t->dense_pb, t->dense_vb1, t->dense_vw2, t->dense_vb2};
-        const int64_t size[12] = {(int64_t)kRowsStem * 16, 128 * 4, 20 * 128 * 4, 20 * 4, (int64_t)kRowsHeadsA * 16, 32 * 4,
-                                  (int64_t)kRowsWp * 16, (int64_t)kRowsWv * 16, 128 * 4, 64 * 4, 64 * 4, 4};
-        p = ptr[index - 4 * t->blocks]; bytes = size[index - 4 * t->blocks];
-    }
-    if (!p) return AF_TOWER_ERR_STATE;                           // its host setter has not run yet
+    if (!t || index < 0 || index >= 4 * t->blocks + kEnds) return AF_TOWER_ERR_ARG;
+    if (!t->set[group_of(index, t->blocks)]) return AF_TOWER_ERR_STATE;          // its host setter has not run yet
+    const int64_t bytes = buffer_bytes(index, t->blocks);
     if (!host_out) return bytes;
     if (cap_bytes < bytes) return AF_TOWER_ERR_ARG;
     TW_HIP_OK(hipSetDevice(t->device));
     TW_HIP_OK(hipDeviceSynchronize());
-    TW_HIP_OK(hipMemcpy(host_out, p, (size_t)bytes, hipMemcpyDeviceToHost));
+    TW_HIP_OK(hipMemcpy(host_out, t->buf[index], (size_t)bytes, hipMemcpyDeviceToHost));
     return bytes;
 }
 

@@ -103,7 +103,8 @@ class HipTower(object):
         S = board_size
         self._xin = self.x[:, :, S:S + S * S, :].unflatten(2, (S, S))      # [B, width/8, S, S, 8] view of the board pixels
 
-    # ---- host setters: fp32 host copies, packed by the library's host loops, buffers re-created (not stream-ordered) ----
+    # ---- host setters: fp32 host copies, staged on the device and packed in place by the kernels load_device runs; they
+    # synchronise the device (not stream-ordered, illegal inside a capture) and keep every buffer's address ----
     @staticmethod
     def _host(tensors):
         keep = [np.ascontiguousarray(t.detach().float().cpu().numpy(), np.float32) for t in tensors]
@@ -169,7 +170,8 @@ class HipTower(object):
         of update_names(blocks); each a contiguous float32 tensor on this handle's device, OIHW convolutions and [in][out] dense
         layers.  Kernels re-pack them in place into the buffers the handle owns, on torch's current stream, behind the forwards
         already queued there: launches only, no wait, legal inside a stream capture.  The tensors must hold their values until
-        the pack kernels have run — a producer on the same stream is ordered."""
+        the pack kernels have run — a producer on the same stream is ordered.  Every host setter must have run once before (the
+        constructor's, when it got all four groups): TowerError with code -3 otherwise."""
         names = update_names(self.blocks)
         if isinstance(tensors, dict):
             missing = [k for k in names if k not in tensors]
@@ -192,7 +194,7 @@ class HipTower(object):
 
     def debug_weights(self):
         """Tests: every weight-derived device buffer of the handle as bytes, in af_tower_debug_weights' order (synchronises);
-        None for a buffer whose host setter has not run."""
+        None for a buffer of a group (a block, stem, heads, dense) whose host setter has not run."""
         out = []
         for i in range(4 * self.blocks + 12):
             size = lib().af_tower_debug_weights(self._h, i, None, 0)

@@ -28,13 +28,19 @@ typedef struct af_tower af_tower;
 #define AF_TOWER_OK 0
 #define AF_TOWER_ERR_ARG   (-1)
 #define AF_TOWER_ERR_HIP   (-2)
-#define AF_TOWER_ERR_STATE (-3)   /* forward / device update before the weights it needs were set through the host setters */
+#define AF_TOWER_ERR_STATE (-3)   /* forward / device update / debug read before the host setter of the weights it needs has run once */
 
 /* board_size must be 11 and width 128 in this build (4 waves x 32 output channels, 4 pixel tiles). */
 int af_tower_create(int32_t board_size, int32_t width, int32_t blocks, int32_t device, af_tower** out);
 void af_tower_destroy(af_tower* t);
 
-/* Weights of block `b` (host pointers, fp32, PyTorch OIHW): c1_w/c2_w [W][W][3][3], res_w [W][W][1][1], biases [W].
+/* The four host setters below take host pointers to fp32 arrays.  Each waits for the device, copies its arrays as they are
+ * into the handle's staging area, runs the device weight packers — the same kernels af_tower_update_device runs — over them on
+ * the null stream and waits again: when it returns the weights are in place and the arrays may be freed.  A setter writes into
+ * buffers the handle has owned since af_tower_create, so no address changes.  It synchronises, so it is not stream-ordered and
+ * is illegal inside a stream capture.
+ *
+ * Weights of block `b` (PyTorch OIHW): c1_w/c2_w [W][W][3][3], res_w [W][W][1][1], biases [W].
  * Values are rounded to bf16 (round-to-nearest-even) when packed. */
 int af_tower_set_block(af_tower* t, int32_t b, const float* c1_w, const float* c1_b, const float* c2_w, const float* c2_b,
                        const float* res_w, const float* res_b);
@@ -68,8 +74,8 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
 
 /* Weight update without the host.  Kernels read fp32 weights from DEVICE memory — the layouts the host setters above take: OIHW
  * convolutions, [in][out] dense layers — and write, in place, every weight-derived buffer the handle owns (fragment streams,
- * biases, b2 = c2_b + res_b, the bf16-rounded dense biases and the fc2 bias word), byte for byte what the host setters make of
- * the same values.  dev_ptrs / counts hold n = 12 + 6 * blocks entries in this fixed order:
+ * biases, b2 = c2_b + res_b, the bf16-rounded dense biases and the fc2 bias word).  They are the kernels the host setters run,
+ * so both paths write the same bytes; oracle/tower_pack.py specifies them.  dev_ptrs / counts hold n = 12 + 6 * blocks entries in this fixed order:
  *     stem_w, stem_b,
  *     per block: c1_w, c1_b, c2_w, c2_b, res_w, res_b,
  *     vconv_w, vconv_b, pconv_w, pconv_b,
@@ -77,8 +83,8 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
  * with element counts stem_w 9600, every 128-wide bias 128, c1_w / c2_w 147456, res_w 16384, vconv_w / vconv_b 512 / 4,
  * pconv_w / pconv_b 2048 / 16, vfc1_w / vfc1_b 30976 / 64, vfc2_w / vfc2_b 64 / 1, pfc_w / pfc_b 234256 / 121.
  * All or nothing, checked before the first launch: a null handle, array or entry, a wrong n or a wrong count is
- * AF_TOWER_ERR_ARG; a handle whose stem, heads, dense layers and every block have not been set once through the host setters
- * (they allocate the buffers) is AF_TOWER_ERR_STATE.
+ * AF_TOWER_ERR_ARG; a handle whose stem, heads, dense layers and every block have not each been set once through the host
+ * setters is AF_TOWER_ERR_STATE.
  * The call is launches only, stream-ordered on `stream`: nothing is freed, allocated or copied to the host, nothing waits, the
  * pointer table travels in kernel arguments (the arrays may go as soon as the call returns; the tensors must hold their values
  * until the kernels have run).  bf16 needs no per-layer scales, so — unlike af_net_update_device — there is nothing to read back.
@@ -86,7 +92,8 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
  * by-value kernel argument:
  *   - a forward graph captured before an update sees the new weights when it is replayed after it;
  *   - [update; forward] may itself be captured and replayed over changed source tensors.
- * A host setter called later replaces (frees and re-creates) its buffers: graphs captured over the handle are stale then. */
+ * The same holds across a host setter called later, outside any capture: it re-packs into the same buffers, so a graph
+ * captured over the handle stays valid and replays with the weights the setter gave. */
 int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_ptrs, const int64_t* counts, int32_t n);
 
 /* Tests: weight-derived device buffer `index` copied to host_out; returns its size in bytes (also with host_out NULL, which

@@ -1,13 +1,15 @@
-"""af_tower_update_device: the bf16 tower's weights re-packed on the device, in place, must be the bytes the host setters
-(af_tower_set_block / _set_stem / _set_heads / _set_dense: host loops, the independent yardstick) make of the same values — every
-buffer of HipTower.debug_weights() — and the update must be what the header says it is: stream-ordered launches only, so a forward
-queued before it sees the old weights, one queued behind it the new ones, a graph captured before it replays with the new weights
-and [update; forward] can itself be captured.  Two blocks throughout: a packer that mixes up blocks is caught.
+"""The bf16 tower's weights, packed by the device packers through either way in — the host setters (af_tower_set_block / _set_stem /
+_set_heads / _set_dense: staged copies, one block or one range of the ends kernel each) and af_tower_update_device (device
+tensors, in place) — must be the bytes oracle/tower_pack.py specifies (numpy, tied to the former host packers' bytes by
+tests/test_tower_pack_cpu.py) in every buffer of HipTower.debug_weights(); a setter must write its own group's buffers and no
+other; and the update must be what the header says it is: stream-ordered launches only, so a forward queued before it sees the
+old weights, one queued behind it the new ones, a graph captured before it — or before a host setter — replays with the new
+weights and [update; forward] can itself be captured.  Two blocks throughout: a packer that mixes up blocks is caught.
 
 Weight sets are Glorot-like random with non-zero biases, all tensors distinct, and carry in every tensor (as far as it has
 room) the fp32 values on which a bf16 conversion can go wrong: exact ties that round down to an even and up from an odd
 mantissa, both signs; +0 and -0; a denormal (1e-40); and — except in the sets a forward runs on — +-3.39e38 (the largest finite
-bf16 after rounding) and +-3.4e38 (inf after rounding)."""
+bf16 after rounding), +-3.4e38 (inf after rounding) and, in the kernels, four NaNs."""
 import ctypes
 
 import numpy as np
@@ -30,11 +32,16 @@ _FINITE_SPECIALS = np.concatenate([_f32([0x3F808000, 0x3F818000, 0x80000000]), n
 # +-3.39e38 lies between the largest finite bf16 (3.3895e38) and the midpoint to 2^128 (3.3961e38): it rounds to that largest
 # finite value, not to inf; +-3.4e38 lies above the midpoint and does overflow to inf.  Both pairs are planted.
 _HUGE_SPECIALS = np.array([3.39e38, -3.39e38, 3.4e38, -3.4e38], np.float32)
+# NaNs, both signs: two quiet ones, and two whose payload lies in the low half only — rounding those like numbers would carry
+# into +-inf.  Planted in tensors of two or more dimensions only: a bias is added (b2 = c2_b + res_b), and which payload an add
+# of NaNs returns is the adder's business, not the packer's.
+_NAN_SPECIALS = _f32([0x7FC00001, 0xFFC00000, 0x7F800001, 0xFF80FFFF])
 
 
 def weight_set(seed, finite, blocks=BLOCKS):
     """{name: float32 array} for a tower of `blocks` blocks (2 unless said).  The specials sit at the same flat positions of every tensor (so b2 = c2_b + res_b
-    never adds infinities of opposite sign); a tensor shorter than the list takes its head."""
+    never adds infinities of opposite sign); a tensor shorter than the list takes its head.  Without `finite`, kernels carry
+    the NaNs behind the rest."""
     from alphafive_amd import network_deep
     rng = np.random.default_rng(seed)
     specials = _FINITE_SPECIALS if finite else np.concatenate([_FINITE_SPECIALS[:4], _HUGE_SPECIALS, _FINITE_SPECIALS[4:]])
@@ -48,8 +55,9 @@ def weight_set(seed, finite, blocks=BLOCKS):
             a = (rng.random(shape) * 2 - 1) * np.sqrt(6.0 / (fan_in + fan_out))
         a = np.ascontiguousarray(a, np.float32)
         flat = a.reshape(-1)
-        n = min(flat.size, specials.size)
-        flat[:n] = specials[:n]
+        mine = specials if finite or len(shape) == 1 else np.concatenate([specials, _NAN_SPECIALS])
+        n = min(flat.size, mine.size)
+        flat[:n] = mine[:n]
         out[name] = a
     return out
 
@@ -70,6 +78,28 @@ def _dense(V):
     import torch
     return tuple(torch.from_numpy(V[n]) for n in ("value/fc1/kernel", "value/fc1/bias", "value/fc2/kernel", "value/fc2/bias",
                                                    "policy/fc/kernel", "policy/fc/bias"))
+
+
+def host_set(tw, V, stem=False, heads=False, dense=False, blocks=()):
+    """The named host setters of the handle, with V's tensors."""
+    import torch
+    pair = lambda n: (torch.from_numpy(V[n + "/kernel"]), torch.from_numpy(V[n + "/bias"]))  # noqa: E731
+    for b in blocks:
+        tw.set_block(b, dict(c1=pair("tower/block%d_conv1" % b), c2=pair("tower/block%d_conv2" % b), res=pair("tower/block%d_res" % b)))
+    if stem:
+        tw.set_stem(pair("stem"))
+    if heads:
+        tw.set_heads(pair("value/conv"), pair("policy/conv"))
+    if dense:
+        tw.set_dense(_dense(V))
+
+
+def assert_buffers(got, want, what):
+    assert len(got) == len(want)
+    for i, (x, y) in enumerate(zip(got, want)):
+        assert x.size == y.size and x.size > 0, "%s: buffer %d has %d bytes, expected %d" % (what, i, x.size, y.size)
+        bad = np.flatnonzero(x != y)
+        assert bad.size == 0, "%s: buffer %d (%d bytes): %d bytes differ, first at %d" % (what, i, x.size, bad.size, bad[0])
 
 
 def on_device(V):
@@ -109,6 +139,13 @@ def sets():
 
 
 @pytest.fixture(scope="module")
+def packed(sets):
+    """oracle.tower_pack.pack_reference of the sets the byte comparisons use, made once."""
+    from oracle.tower_pack import pack_reference
+    return {k: pack_reference(sets[k], BLOCKS) for k in ("V", "V0", "V1")}
+
+
+@pytest.fixture(scope="module")
 def refs(sets):
     """Outputs of fresh host-set handles on the 32 positions, per finite weight set."""
     import torch
@@ -130,29 +167,37 @@ def test_specials_are_what_they_claim():
     huge = _HUGE_SPECIALS.view(np.uint32) & 0x7FFFFFFF
     assert np.isfinite(_FINITE_SPECIALS).all() and np.isfinite(_HUGE_SPECIALS).all() and (huge >> 16 == 0x7F7F).all()
     assert (huge[:2] & 0xFFFF < 0x8000).all() and (huge[2:] & 0xFFFF > 0x8000).all()        # 3.39e38 stays finite, 3.4e38 overflows
+    nans = _NAN_SPECIALS.view(np.uint32)
+    assert np.isnan(_NAN_SPECIALS).all() and sorted(int(b) >> 31 for b in nans) == [0, 0, 1, 1]
+    assert sum(1 for b in nans if b & 0x7FFF0000 == 0x7F800000) == 2       # the payload in the low half only: rounded like a number, +-inf
     V = weight_set(10, False)
+    for name, v in V.items():                                              # NaNs in every kernel, in no bias, and in no finite set
+        assert np.isnan(v).sum() == (4 if v.ndim > 1 else 0), name
+        assert set(v.reshape(-1)[np.isnan(v.reshape(-1))].view(np.uint32).tolist()) == (set(nans.tolist()) if v.ndim > 1 else set()), name
+    assert not any(np.isnan(v).any() for v in weight_set(20, True).values())
     assert len(V) == 12 + 6 * BLOCKS and all(v.reshape(-1)[0].view(np.uint32) == 0x3F808000 for v in V.values())
     assert not np.array_equal(V["tower/block0_conv1/kernel"], V["tower/block1_conv1/kernel"])
     assert not np.array_equal(V["tower/block0_conv2/bias"], V["tower/block1_conv2/bias"])
 
 
-def test_device_packers_write_the_host_setters_bytes(sets):
+def test_device_packers_write_the_host_setters_bytes(sets, packed):
+    """Handle A through the host setters, handle B through load_device: both hold the specification's bytes."""
     import torch
     A, B = host_tower(sets["V"]), host_tower(sets["U"])
     try:
         before = B.debug_weights()
         B.load_device(on_device(sets["V"]))
         a, b = A.debug_weights(), B.debug_weights()
-        assert len(a) == len(b) == NBUF
+        assert len(a) == len(b) == len(packed["V"]) == NBUF
         changed = sum(1 for x, y in zip(before, b) if not np.array_equal(x, y))
         assert changed > 4 * BLOCKS + 6, changed                       # not two untouched copies
-        for i, (x, y) in enumerate(zip(a, b)):
-            assert x.size == y.size and x.size > 0
-            bad = np.flatnonzero(x != y)
-            assert bad.size == 0, "buffer %d (%d bytes): %d bytes differ, first at %d" % (i, x.size, bad.size, bad[0])
+        assert_buffers(a, packed["V"], "host setters")
+        assert_buffers(b, packed["V"], "load_device")
         w1 = a[0].view(np.uint16)
         assert (w1 == 0x7F80).any() and (w1 == 0xFF80).any() and (w1 == 0x8000).any()     # inf both ways and -0 made it into the fragments
         assert (w1 == 0x7F7F).any() and (w1 == 0xFF7F).any() and (w1 == 0x3E00).any()     # 3.39e38 did not overflow; the carry into the exponent
+        assert (w1 == 0x7FC0).any() and (w1 == 0xFFC0).any()                              # NaNs stayed NaNs, signs kept ...
+        assert np.count_nonzero(w1 == 0x7F80) == 1 and np.count_nonzero(w1 == 0xFF80) == 1    # ... none turned into a second +-inf
         assert a[4 * BLOCKS + 11].size == 4                            # dense_vb2 is a device word
         torch.cuda.synchronize()
     finally:
@@ -165,23 +210,73 @@ def test_device_packers_write_the_host_setters_bytes_at_full_depth(blocks):
     """The depth the feature exists for — 8 blocks (BASELINE configs[4]): every block slot of one pack launch filled — and 9, which
     takes a second launch for the block past the eighth.  Same byte-for-byte comparison as above."""
     import torch
+    from oracle.tower_pack import pack_reference
     V = weight_set(30 + blocks, False, blocks)
+    want = pack_reference(V, blocks)
     A, B = host_tower(V, max_batch=1, blocks=blocks), host_tower(weight_set(40 + blocks, True, blocks), max_batch=1, blocks=blocks)
     try:
         before = B.debug_weights()
         B.load_device(on_device(V))
         a, b = A.debug_weights(), B.debug_weights()
-        assert len(a) == len(b) == 4 * blocks + 12
+        assert len(a) == len(b) == len(want) == 4 * blocks + 12
         assert all(not np.array_equal(x, y) for x, y in zip(before[:4 * blocks], b[:4 * blocks]))      # every block's four buffers were written
-        for i, (x, y) in enumerate(zip(a, b)):
-            bad = np.flatnonzero(x != y)
-            assert x.size == y.size and bad.size == 0, "buffer %d (%d bytes): %d bytes differ" % (i, x.size, bad.size)
+        assert_buffers(a, want, "host setters")
+        assert_buffers(b, want, "load_device")
         for i in range(4):                               # ... each with its own block's weights
             assert len({a[4 * blk + i].tobytes() for blk in range(blocks)}) == blocks
         torch.cuda.synchronize()
     finally:
         A.close()
         B.close()
+
+
+def test_a_host_setter_writes_its_own_buffers_only(sets, packed):
+    """Each setter launches one block or one range of the ends kernel, with the other groups' source pointers null: on a fully
+    set handle holding V0, a setter given V1's tensors must leave its own buffers as V1 packs and every other buffer as V0 does
+    — a range one thread too long or too short shows in the neighbour's first or its own last word."""
+    E = 4 * BLOCKS                                                  # stem_w, stem_b | heads_w, heads_b, heads_a, heads_b32 | dense_*
+    steps = [("set_heads", dict(heads=True), range(E + 2, E + 6)), ("set_stem", dict(stem=True), range(E, E + 2)),
+             ("set_dense", dict(dense=True), range(E + 6, E + 12)), ("set_block(1)", dict(blocks=(1,)), range(4, 8))]
+    tw = host_tower(sets["V0"])
+    try:
+        want = list(packed["V0"])
+        assert_buffers(tw.debug_weights(), want, "V0")
+        for what, groups, own in steps:
+            host_set(tw, sets["V1"], **groups)
+            for i in own:
+                # the step has something to show (dense_vb2 is one word, the special every tensor starts with, in both sets)
+                assert want[i].size == 4 or not np.array_equal(want[i], packed["V1"][i]), i
+                want[i] = packed["V1"][i]
+            assert_buffers(tw.debug_weights(), want, what)
+    finally:
+        tw.close()
+
+
+def test_captured_forward_sees_later_host_setters(sets, refs):
+    """The host setters write into the buffers the handle has owned since it was created: a graph captured over it replays with
+    the weights they gave."""
+    import torch
+    x, out = refs
+    tw = host_tower(sets["V0"])
+    try:
+        forward(tw, x)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            tw.stem(x)
+            tw.forward(MAXB)
+            tw.heads(MAXB)
+            tw.dense(MAXB)
+        g.replay()
+        torch.cuda.synchronize()
+        assert same_bits((tw.policy, tw.value), out["V0"])
+        host_set(tw, sets["V1"], stem=True, heads=True, dense=True, blocks=range(BLOCKS))
+        g.replay()
+        torch.cuda.synchronize()
+        assert same_bits((tw.policy, tw.value), out["V1"])
+        del g
+    finally:
+        tw.close()
 
 
 @pytest.mark.parametrize("engine", [3, 0], ids=["default", "tune(3, 0)"])

@@ -1,7 +1,8 @@
 """What does giving the bf16 tower (BASELINE configs[4]: 8 blocks x 128, an evaluator sized for 8192 positions) a new weight set cost?
   (a) device  HipTower.load_device(tensors)       — af_tower_update_device: the pack kernels over fp32 device tensors, in place
-  (b) host    DeepResNet.select_backend("hip", G) — the only way before load_device: a new handle through the host setters (tensors to
-              the host, host packing loops, one allocation + synchronous copy per buffer) and new activation buffers
+  (b) host    DeepResNet.select_backend("hip", G) — the only way before load_device: a new handle (one allocation) through the host
+              setters (tensors to the host, a synchronous copy into the handle's staging area and the same pack kernels, eleven
+              times) and new activation buffers
 Both in one process, alternated over five rounds after warm-up.  (a): device events around 20 back-to-back calls (per-call mean of the
 window) and around 20 single calls; (b): host clock between two device synchronisations.  Also DeepResNet.set_variables_device (the
 copies into the net's own tensors + load_device) and the host-side enqueue time of one load_device.  Prints one JSON line; the ratio
