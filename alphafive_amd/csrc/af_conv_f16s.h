@@ -13,9 +13,11 @@ struct f16s_net;
 // board sizes 11 (one pseudo-position per board) and 15 (two half-board pseudo-positions per board); on both the heads are fused (the
 // 1x1 head convolutions ride the last conv of each branch, the dense layers run on af_value_fc_f16s / af_policy_fc_f16s<Geo<S>>)
 int f16s_supported(int board_size);
-// allocates every device buffer of the handle; the weight-derived ones hold nothing until the first f16s_update_pack
+// allocates every device buffer of the handle, once (af_net_create); the weight-derived ones hold nothing until the first f16s_update_pack
 int f16s_create(f16s_net** out, int board_size, int max_batch, int device);
 void f16s_destroy(f16s_net* n);
+// zeroes the role counters of kF16sRoles and what f16s_small_forward_error reports (af_net_finalize, behind its device wait)
+int f16s_reset_roles(f16s_net* n);
 // ---- the launch plan: which launches a forward of `batch` positions is made of ----
 // af_net_tune key 7 (include/af_net.h describes the bits by these names).  The profiling bits reach the kernels (F16sArgs::abl) and
 // make the results wrong by design; every other bit selects the launch structure the default replaced.

@@ -1910,8 +1910,9 @@ static int dev_alloc(f16s_net* n, T** dst, size_t bytes, bool zero) {
 }
 
 // Picks the geometry and allocates every device buffer of the handle; it packs nothing.  The weight-derived buffers are filled, and
-// the inverse scales set, by f16s_update_pack (af_net_finalize runs it over the staged variables before any forward).  wbuf registers
-// each weight-derived buffer for f16s_weight_buffer as it allocates it, so what is allocated and what is reported cannot differ:
+// the inverse scales set, by f16s_update_pack (af_net_finalize runs it over the staged variables before any forward).  af_net_create
+// calls this once per handle; a weight load re-creates nothing.  wbuf registers each weight-derived buffer for f16s_weight_buffer
+// as it allocates it, so what is allocated and what is reported cannot differ:
 //   stem_w, stem_b, stem_wm, w[0..9], pw[4], pw[8], bias[0..9], hcw[0..1], hcb[0..1], hfw[0..1], hfb[0..1], v2w, v2b
 int f16s_create(f16s_net** out, int board_size, int max_batch, int device) {
     if (!f16s_supported(board_size)) return -1;
@@ -1966,6 +1967,12 @@ void f16s_destroy(f16s_net* n) {
     (void)hipSetDevice(n->device);
     for (void* p : n->allocs) (void)hipFree(p);
     delete n;
+}
+
+// a host weight load starts the role counters and their give-up flag afresh (the caller has waited for the device)
+int f16s_reset_roles(f16s_net* n) {
+    FS_HIP_OK(hipMemset(n->df, 0, kDfWords * sizeof(int)));
+    return 0;
 }
 
 

@@ -593,39 +593,67 @@ struct Block { const char* name; int cin, cout; };
 static const Block kBlocks[5] = {{"bone/block1", 32, 64}, {"bone/block2", 64, 128}, {"value/block3", 128, 32},
                                  {"policy/block4", 128, 64}, {"policy/block5", 64, 32}};
 
+// The 42 variables in the order of the staging area: the stem's two, the ten of the heads, six per block.
+// Element count = c0 + c1 * HW + c2 * HW * HW.
+enum { kVarHeads = 2, kVarBlocks = kVarHeads + 10, kVars = kVarBlocks + 6 * 5, kC1K = 0, kC1B, kC2K, kC2B, kResK, kResB };
+struct Var { std::string name; int c0, c1, c2; };
+static const std::vector<Var>& variables() {
+    static const std::vector<Var> table = [] {
+        std::vector<Var> t = {{"bone/conv1/kernel", 75 * 32}, {"bone/conv1/bias", 32}, {"value/conv/kernel", 32 * 4}, {"value/conv/bias", 4},
+                              {"value/fc1/kernel", 0, 4 * 64}, {"value/fc1/bias", 64}, {"value/fc2/kernel", 64}, {"value/fc2/bias", 1},
+                              {"policy/conv/kernel", 32 * 16}, {"policy/conv/bias", 16}, {"policy/fc/kernel", 0, 0, 16}, {"policy/fc/bias", 0, 1}};
+        for (const Block& b : kBlocks)
+            for (const Var& v : {Var{"_conv1/kernel", 9 * b.cin * b.cout}, Var{"_conv1/bias", b.cout}, Var{"_conv2/kernel", 9 * b.cout * b.cout},
+                                 Var{"_conv2/bias", b.cout}, Var{"_res/kernel", b.cin * b.cout}, Var{"_res/bias", b.cout}})
+                t.push_back({b.name + v.name, v.c0});
+        return t;
+    }();
+    return table;
+}
+static int var_index(const char* name) {
+    for (int i = 0; i < kVars; ++i) if (variables()[i].name == name) return i;
+    return -1;
+}
+static size_t var_count(int i, int HW) { const Var& v = variables()[i]; return v.c0 + (size_t)v.c1 * HW + (size_t)v.c2 * HW * HW; }
+static size_t var_offset(int i, int HW) {        // in floats; var_offset(kVars, HW) = the size of the staging area
+    size_t at = 0;
+    for (int k = 0; k < i; ++k) at += var_count(k, HW);
+    return at;
+}
+
+// The fp32 path's weight-derived buffers in af_net_debug_weights' order (the split-operand path's follow: f16s_weight_buffer): stem
+// kernel and bias; per block the padded conv1 bias, the padded conv2 + projection bias and the Winograd-domain conv1 / conv2 /
+// projection kernels; the heads' ten tensors as they are, in the variables' order.
+enum { kStemW, kStemB, kConv1B, kSumB = kConv1B + 5, kWino1 = kSumB + 5, kWino2 = kWino1 + 5, kWinoR = kWino2 + 5, kHeadW = kWinoR + 5,
+       kVcW = kHeadW, kVcB, kV1W, kV1B, kV2W, kV2B, kPcW, kPcB, kPfW, kPfB, kWeightBufs };
+static size_t weight_count(int i, int HW) {
+    if (i < kConv1B) return var_count(i, HW);
+    if (i >= kHeadW) return var_count(kVarHeads + i - kHeadW, HW);
+    const Block& b = kBlocks[(i - kConv1B) % 5];
+    if (i < kWino1) return (b.cout + 31) / 32 * 32;          // biases are padded to a multiple of 32 couts
+    if (i < kWino2) return (size_t)b.cin * b.cout * 16;
+    return i < kWinoR ? (size_t)b.cout * b.cout * 16 : (size_t)b.cin * b.cout * 4;
+}
+// ... and its activation buffers [max_batch][C][PP]: the stem's output, then per block g (conv1's output) and o (the block's)
+enum { kF0, kG, kO, kActs = 1 + 2 * 5 };
+static int act_channels(int i) { return i == kF0 ? 32 : kBlocks[(i - kG) / 2].cout; }
+
+// Everything a handle owns is made by af_net_create and lives until af_net_destroy; no call in between allocates or frees.
 struct af_net {
-    int S, HW, WP, PP, max_batch, device;
-    bool ready = false;
-    std::map<std::string, std::vector<float>> vars;
-    std::map<std::string, size_t> expect;
-    std::vector<void*> allocs;
-    // device weights
-    float *stem_w, *stem_b;
-    float *conv1_b[5], *sum_b[5];
-    float *wino1_u[5], *wino2_u[5], *winor_u[5];
-    int T;
+    int S, HW, WP, PP, T, max_batch, device;
+    // state.  set: af_net_set_variable marks a variable, af_net_update_device clears them all (the host image is stale then);
+    // packed and ready: pack_from_device sets both, af_net_set_variable takes ready back until the next af_net_finalize
+    bool set[kVars] = {}, packed = false, ready = false;
+    std::vector<float> image;     // host image of the staging area
+    float* arena = nullptr;       // one allocation: stage, upd_max_dev and w[] at 256-byte offsets
+    float* stage = nullptr;       // the 42 fp32 variables as af_net_finalize uploads them: what its pack kernels read
+    float *upd_max_dev = nullptr, *upd_max_host = nullptr;      // max|w| per scale group of the split-operand path, device and pinned host
+    float* w[kWeightBufs] = {};
+    float* act[kActs] = {};       // zero-filled once: no kernel writes their borders
     hipStream_t branch_stream = nullptr;
     hipEvent_t ev_trunk = nullptr, ev_value = nullptr;
-    float *vc_w, *vc_b, *v1_w, *v1_b, *v2_w, *v2_b, *pc_w, *pc_b, *pf_w, *pf_b;
-    // activations [max_batch][C][PP]
-    float *f0, *g[5], *o[5];
-    f16s_net* f16s = nullptr;     // 11x11 boards: the fp16 split-operand convolution path (af_conv_f16s.hip)
-    // weight packing: max|w| per scale group of the split-operand path, device and pinned host (created once, by the first finalize)
-    float *upd_max_dev = nullptr, *upd_max_host = nullptr;
-    std::vector<std::pair<const void*, size_t>> wreg;   // weight-derived buffers of this path, in af_net_debug_weights' order
+    f16s_net* f16s = nullptr;     // 11x11 and 15x15 boards: the fp16 split-operand convolution path (af_conv_f16s.hip)
 };
-
-static int pad32(int c) { return (c + 31) / 32 * 32; }
-
-template <typename T>
-static int net_alloc(af_net* n, T** p, size_t count, bool zero) {
-    void* q = nullptr;
-    NET_HIP_OK(hipMalloc(&q, count * sizeof(T)));
-    if (zero) NET_HIP_OK(hipMemset(q, 0, count * sizeof(T)));
-    n->allocs.push_back(q);
-    *p = (T*)q;
-    return AF_NET_OK;
-}
 
 // Winograd weights U = G g G^T per (cin, cout), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], packed [cin/2][2][cout][npos] (one
 // lane's npos values contiguous).  taps == 9: all 16 (xi,nu); taps == 1: the centre-tap kernel of a 1x1 projection, whose only
@@ -668,11 +696,13 @@ __global__ __launch_bounds__(256) void af_update_wino(WinoPackTable T) {
     }
 }
 
-// Packs every weight-derived buffer of the handle, in place, from the 42 fp32 TF-layout tensors D names in device memory: the one
-// packer behind af_net_finalize and af_net_update_device.  Asynchronous on st but for ONE wait: the scales of the split-operand
-// path need max|w| per group, reduced on the device and brought to the host as 80 bytes.
-static int pack_from_device(af_net* n, hipStream_t st, const f16s_dev_vars& D) {
+// Packs every weight-derived buffer of the handle, in place, from the 42 fp32 TF-layout tensors src names in device memory
+// (variables()' order): the one packer behind af_net_finalize and af_net_update_device.  Asynchronous on st but for ONE wait: the
+// scales of the split-operand path need max|w| per group, reduced on the device and brought to the host as 80 bytes.
+static int pack_from_device(af_net* n, hipStream_t st, const float* const* src) {
     if (n->f16s) {
+        f16s_dev_vars D;
+        for (int i = 0; i < kVars; ++i) D[variables()[i].name] = src[i];
         if (f16s_update_absmax(n->f16s, st, D, n->upd_max_dev)) return AF_NET_ERR_HIP;
         NET_HIP_OK(hipMemcpyAsync(n->upd_max_host, n->upd_max_dev, kF16sScaleGroups * sizeof(float), hipMemcpyDeviceToHost, st));
         NET_HIP_OK(hipStreamSynchronize(st));
@@ -681,29 +711,51 @@ static int pack_from_device(af_net* n, hipStream_t st, const f16s_dev_vars& D) {
     WinoPackTable W = {};
     UpdCopy C[22];
     int ncp = 0;
-    auto copy = [&](float* dst, const char* a, const float* b, size_t n_dst, int sum) {
-        C[ncp++] = UpdCopy{dst, D.at(a), b, (int)n_dst, (int)n->expect.at(a), sum};
+    auto copy = [&](int buf, int var, const float* b, int sum) {
+        C[ncp++] = UpdCopy{n->w[buf], src[var], b, (int)weight_count(buf, n->HW), (int)var_count(var, n->HW), sum};
     };
-    copy(n->stem_w, "bone/conv1/kernel", nullptr, 75 * 32, 0); copy(n->stem_b, "bone/conv1/bias", nullptr, 32, 0);
+    copy(kStemW, 0, nullptr, 0); copy(kStemB, 1, nullptr, 0);
     for (int i = 0; i < 5; ++i) {
         const Block& b = kBlocks[i];
-        const std::string s = b.name;
+        const int v = kVarBlocks + 6 * i;
         // biases padded with zeros to a multiple of 32 couts; conv1's is bias + 0.0f, conv2's the sum with the projection's
-        copy(n->conv1_b[i], (s + "_conv1/bias").c_str(), nullptr, pad32(b.cout), 1);
-        copy(n->sum_b[i], (s + "_conv2/bias").c_str(), D.at(s + "_res/bias"), pad32(b.cout), 1);
-        W.d[3 * i] = WinoPackDesc{D.at(s + "_conv1/kernel"), n->wino1_u[i], 9, b.cin, b.cout};
-        W.d[3 * i + 1] = WinoPackDesc{D.at(s + "_conv2/kernel"), n->wino2_u[i], 9, b.cout, b.cout};
-        W.d[3 * i + 2] = WinoPackDesc{D.at(s + "_res/kernel"), n->winor_u[i], 1, b.cin, b.cout};
+        copy(kConv1B + i, v + kC1B, nullptr, 1);
+        copy(kSumB + i, v + kC2B, src[v + kResB], 1);
+        W.d[3 * i] = WinoPackDesc{src[v + kC1K], n->w[kWino1 + i], 9, b.cin, b.cout};
+        W.d[3 * i + 1] = WinoPackDesc{src[v + kC2K], n->w[kWino2 + i], 9, b.cout, b.cout};
+        W.d[3 * i + 2] = WinoPackDesc{src[v + kResK], n->w[kWinoR + i], 1, b.cin, b.cout};
     }
-    const size_t HW = n->HW;
-    copy(n->vc_w, "value/conv/kernel", nullptr, 32 * 4, 0); copy(n->vc_b, "value/conv/bias", nullptr, 4, 0);
-    copy(n->v1_w, "value/fc1/kernel", nullptr, 4 * HW * 64, 0); copy(n->v1_b, "value/fc1/bias", nullptr, 64, 0);
-    copy(n->v2_w, "value/fc2/kernel", nullptr, 64, 0); copy(n->v2_b, "value/fc2/bias", nullptr, 1, 0);
-    copy(n->pc_w, "policy/conv/kernel", nullptr, 32 * 16, 0); copy(n->pc_b, "policy/conv/bias", nullptr, 16, 0);
-    copy(n->pf_w, "policy/fc/kernel", nullptr, 16 * HW * HW, 0); copy(n->pf_b, "policy/fc/bias", nullptr, HW, 0);
+    for (int j = 0; j < 10; ++j) copy(kHeadW + j, kVarHeads + j, nullptr, 0);
     hipLaunchKernelGGL(af_update_wino, dim3(kWinoPackBlocks, kWinoBufs), dim3(256), 0, st, W);
     NET_HIP_OK(hipGetLastError());
     if (upd_launch_copies(st, C, ncp)) return AF_NET_ERR_HIP;
+    n->packed = n->ready = true;
+    return AF_NET_OK;
+}
+
+// af_net_create's device half (no forward runs before an af_net_finalize, which waits for the device: the zero-fills have finished by then)
+static int allocate(af_net* n) {
+    NET_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_head_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   160 * 1024));
+    auto pad64 = [](size_t count) { return (count + 63) & ~(size_t)63; };       // floats: every buffer of the arena starts at a 256-byte offset
+    n->image.resize(var_offset(kVars, n->HW));
+    size_t total = pad64(n->image.size()) + pad64(kF16sScaleGroups);
+    for (int i = 0; i < kWeightBufs; ++i) total += pad64(weight_count(i, n->HW));
+    NET_HIP_OK(hipMalloc((void**)&n->arena, total * sizeof(float)));
+    n->stage = n->arena;
+    n->upd_max_dev = n->stage + pad64(n->image.size());
+    float* p = n->upd_max_dev + pad64(kF16sScaleGroups);
+    for (int i = 0; i < kWeightBufs; ++i) { n->w[i] = p; p += pad64(weight_count(i, n->HW)); }
+    NET_HIP_OK(hipHostMalloc((void**)&n->upd_max_host, kF16sScaleGroups * sizeof(float), hipHostMallocDefault));
+    for (int i = 0; i < kActs; ++i) {
+        const size_t bytes = (size_t)n->max_batch * n->PP * act_channels(i) * sizeof(float);
+        NET_HIP_OK(hipMalloc((void**)&n->act[i], bytes));
+        NET_HIP_OK(hipMemset(n->act[i], 0, bytes));
+    }
+    NET_HIP_OK(hipStreamCreateWithFlags(&n->branch_stream, hipStreamNonBlocking));
+    NET_HIP_OK(hipEventCreateWithFlags(&n->ev_trunk, hipEventDisableTiming));
+    NET_HIP_OK(hipEventCreateWithFlags(&n->ev_value, hipEventDisableTiming));
+    if (f16s_supported(n->S) && f16s_create(&n->f16s, n->S, n->max_batch, n->device) != 0) return AF_NET_ERR_HIP;
     return AF_NET_OK;
 }
 
@@ -731,19 +783,8 @@ int af_net_create(int32_t S, int32_t max_batch, int32_t device, af_net** out) {
     n->max_batch = max_batch; n->device = device;
     // the conv kernels address activations with 32-bit byte offsets: the widest buffer must stay below 4 GiB
     if ((uint64_t)max_batch * 128u * (uint64_t)n->PP * 4u >= (1ull << 32)) { delete n; return AF_NET_ERR_ARG; }
-    const size_t HW = n->HW;
-    n->expect["bone/conv1/kernel"] = 75 * 32; n->expect["bone/conv1/bias"] = 32;
-    for (const Block& b : kBlocks) {
-        const std::string s = b.name;
-        n->expect[s + "_res/kernel"] = (size_t)b.cin * b.cout; n->expect[s + "_res/bias"] = b.cout;
-        n->expect[s + "_conv1/kernel"] = (size_t)9 * b.cin * b.cout; n->expect[s + "_conv1/bias"] = b.cout;
-        n->expect[s + "_conv2/kernel"] = (size_t)9 * b.cout * b.cout; n->expect[s + "_conv2/bias"] = b.cout;
-    }
-    n->expect["value/conv/kernel"] = 32 * 4; n->expect["value/conv/bias"] = 4;
-    n->expect["value/fc1/kernel"] = 4 * HW * 64; n->expect["value/fc1/bias"] = 64;
-    n->expect["value/fc2/kernel"] = 64; n->expect["value/fc2/bias"] = 1;
-    n->expect["policy/conv/kernel"] = 32 * 16; n->expect["policy/conv/bias"] = 16;
-    n->expect["policy/fc/kernel"] = 16 * HW * HW; n->expect["policy/fc/bias"] = HW;
+    const int rc = allocate(n);
+    if (rc) { af_net_destroy(n); return rc; }
     *out = n;
     return AF_NET_OK;
 }
@@ -751,9 +792,9 @@ int af_net_create(int32_t S, int32_t max_batch, int32_t device, af_net** out) {
 void af_net_destroy(af_net* n) {
     if (!n) return;
     (void)hipSetDevice(n->device);
-    for (void* p : n->allocs) (void)hipFree(p);
     f16s_destroy(n->f16s);
-    if (n->upd_max_dev) (void)hipFree(n->upd_max_dev);
+    (void)hipFree(n->arena);
+    for (float* a : n->act) (void)hipFree(a);
     if (n->upd_max_host) (void)hipHostFree(n->upd_max_host);
     if (n->branch_stream) (void)hipStreamDestroy(n->branch_stream);
     if (n->ev_trunk) (void)hipEventDestroy(n->ev_trunk);
@@ -763,106 +804,60 @@ void af_net_destroy(af_net* n) {
 
 int af_net_set_variable(af_net* n, const char* name, const float* data, int64_t count) {
     if (!n || !name || !data) return AF_NET_ERR_ARG;
-    auto it = n->expect.find(name);
-    if (it == n->expect.end() || (int64_t)it->second != count) return AF_NET_ERR_NAME;
-    n->vars[name].assign(data, data + count);
+    const int v = var_index(name);
+    if (v < 0 || (int64_t)var_count(v, n->HW) != count) return AF_NET_ERR_NAME;
+    memcpy(n->image.data() + var_offset(v, n->HW), data, (size_t)count * sizeof(float));
+    n->set[v] = true;
     n->ready = false;
     return AF_NET_OK;
 }
 
 int af_net_finalize(af_net* n) {
     if (!n) return AF_NET_ERR_ARG;
-    for (auto& kv : n->expect) if (!n->vars.count(kv.first)) return AF_NET_ERR_STATE;
+    for (bool s : n->set) if (!s) return AF_NET_ERR_STATE;
     NET_HIP_OK(hipSetDevice(n->device));
-    for (void* p : n->allocs) (void)hipFree(p);
-    n->allocs.clear();
-    f16s_destroy(n->f16s);
-    n->f16s = nullptr;
-    if (f16s_supported(n->S) && f16s_create(&n->f16s, n->S, n->max_batch, n->device) != 0) return AF_NET_ERR_HIP;
-    int rc = AF_NET_OK;
-    // the fp32 path's weight-derived buffers, registered in af_net_debug_weights' order as they are allocated (the split-operand
-    // path's follow: f16s_weight_buffer), so what is allocated and what af_net_debug_weights reports cannot differ; pack_from_device fills them
-    n->wreg.clear();
-    auto wbuf = [&](float** p, size_t count) {
-        if (!rc) rc = net_alloc(n, p, count, false);
-        if (!rc) n->wreg.push_back({*p, count * sizeof(float)});
-    };
-    const size_t HW = n->HW;
-    wbuf(&n->stem_w, 75 * 32); wbuf(&n->stem_b, 32);
-    for (int i = 0; i < 5; ++i) wbuf(&n->conv1_b[i], pad32(kBlocks[i].cout));
-    for (int i = 0; i < 5; ++i) wbuf(&n->sum_b[i], pad32(kBlocks[i].cout));
-    for (int i = 0; i < 5; ++i) wbuf(&n->wino1_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 16);
-    for (int i = 0; i < 5; ++i) wbuf(&n->wino2_u[i], (size_t)kBlocks[i].cout * kBlocks[i].cout * 16);
-    for (int i = 0; i < 5; ++i) wbuf(&n->winor_u[i], (size_t)kBlocks[i].cin * kBlocks[i].cout * 4);
-    wbuf(&n->vc_w, 32 * 4); wbuf(&n->vc_b, 4); wbuf(&n->v1_w, 4 * HW * 64); wbuf(&n->v1_b, 64); wbuf(&n->v2_w, 64); wbuf(&n->v2_b, 1);
-    wbuf(&n->pc_w, 32 * 16); wbuf(&n->pc_b, 16); wbuf(&n->pf_w, 16 * HW * HW); wbuf(&n->pf_b, HW);
-    const size_t plane = (size_t)n->max_batch * n->PP;
-    if (!rc) rc = net_alloc(n, &n->f0, plane * 32, true);
-    for (int i = 0; i < 5 && !rc; ++i) {
-        rc = net_alloc(n, &n->g[i], plane * kBlocks[i].cout, true);
-        if (!rc) rc = net_alloc(n, &n->o[i], plane * kBlocks[i].cout, true);
-    }
+    NET_HIP_OK(hipDeviceSynchronize());          // forwards in flight, on any stream, still read the buffers
+    if (n->f16s && f16s_reset_roles(n->f16s)) return AF_NET_ERR_HIP;
+    NET_HIP_OK(hipMemcpy(n->stage, n->image.data(), n->image.size() * sizeof(float), hipMemcpyHostToDevice));
+    const float* src[kVars];
+    for (int i = 0; i < kVars; ++i) src[i] = n->stage + var_offset(i, n->HW);
+    const int rc = pack_from_device(n, nullptr, src);
     if (rc) return rc;
-    NET_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_policy_head_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-    if (!n->branch_stream) {
-        NET_HIP_OK(hipStreamCreateWithFlags(&n->branch_stream, hipStreamNonBlocking));
-        NET_HIP_OK(hipEventCreateWithFlags(&n->ev_trunk, hipEventDisableTiming));
-        NET_HIP_OK(hipEventCreateWithFlags(&n->ev_value, hipEventDisableTiming));
-    }
-    if (!n->upd_max_dev) {       // af_net_update_device allocates nothing: the packer's two small buffers are made here, once per handle
-        NET_HIP_OK(hipMalloc((void**)&n->upd_max_dev, kF16sScaleGroups * sizeof(float)));
-        NET_HIP_OK(hipHostMalloc((void**)&n->upd_max_host, kF16sScaleGroups * sizeof(float), hipHostMallocDefault));
-    }
-    // stage the variables on the device in n->vars' order — one host image, one allocation, one copy — and pack from there
-    std::vector<float> image;
-    for (auto& kv : n->vars) image.insert(image.end(), kv.second.begin(), kv.second.end());
-    float* stage = nullptr;
-    NET_HIP_OK(hipMalloc((void**)&stage, image.size() * sizeof(float)));
-    f16s_dev_vars D;
-    size_t off = 0;
-    for (auto& kv : n->vars) { D[kv.first] = stage + off; off += kv.second.size(); }
-    rc = hipMemcpy(stage, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? AF_NET_OK : AF_NET_ERR_HIP;
-    if (!rc) rc = pack_from_device(n, nullptr, D);
-    // every pack kernel has finished before this returns: a forward on any stream finds the weights, and the staging can go
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = AF_NET_ERR_HIP;
-    (void)hipFree(stage);
-    n->ready = rc == AF_NET_OK;
-    return rc;
+    NET_HIP_OK(hipStreamSynchronize(nullptr));   // every pack kernel has finished: a forward on any stream finds the weights
+    return AF_NET_OK;
 }
 
 int af_net_update_device(af_net* n, void* stream, const char* const* tf_names, const float* const* dev_ptrs, const int64_t* counts,
                          int32_t nvars) {
     if (!n || !tf_names || !dev_ptrs || !counts) return AF_NET_ERR_ARG;            // (before any HIP call)
-    if (n->allocs.empty()) return AF_NET_ERR_STATE;                                // never finalized: there are no buffers to write into
+    if (!n->packed) return AF_NET_ERR_STATE;                                       // never finalized
     // all or nothing: every name known, every count right, all variables present exactly once — before anything is launched
-    if (nvars != (int32_t)n->expect.size()) return AF_NET_ERR_ARG;
-    f16s_dev_vars D;
+    if (nvars != kVars) return AF_NET_ERR_ARG;
+    const float* src[kVars] = {};
     for (int i = 0; i < nvars; ++i) {
         if (!tf_names[i] || !dev_ptrs[i]) return AF_NET_ERR_ARG;
-        auto it = n->expect.find(tf_names[i]);
-        if (it == n->expect.end() || (int64_t)it->second != counts[i]) return AF_NET_ERR_NAME;
-        if (!D.emplace(it->first, dev_ptrs[i]).second) return AF_NET_ERR_ARG;      // a name twice (so another one is missing)
+        const int v = var_index(tf_names[i]);
+        if (v < 0 || (int64_t)var_count(v, n->HW) != counts[i]) return AF_NET_ERR_NAME;
+        if (src[v]) return AF_NET_ERR_ARG;                                         // a name twice (so another one is missing)
+        src[v] = dev_ptrs[i];
     }
     hipStream_t st = (hipStream_t)stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     NET_HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return AF_NET_ERR_STATE;                // this call waits for the stream once: not capturable
     NET_HIP_OK(hipSetDevice(n->device));
-    const int rc = pack_from_device(n, st, D);
+    const int rc = pack_from_device(n, st, src);
     if (rc) return rc;
-    n->vars.clear();             // the host copy is stale: af_net_finalize needs all 42 variables set again
-    n->ready = true;
+    for (bool& s : n->set) s = false;        // the host image is stale: af_net_finalize needs all 42 variables set again
     return AF_NET_OK;
 }
 
 int64_t af_net_debug_weights(af_net* n, int32_t index, void* host_out, int64_t cap_bytes) {
-    if (!n || index < 0 || n->allocs.empty()) return AF_NET_ERR_ARG;
+    if (!n || index < 0 || !n->packed) return AF_NET_ERR_ARG;
     const void* p = nullptr;
     size_t bytes = 0;
-    const int n32 = (int)n->wreg.size();
-    if (index < n32) { p = n->wreg[index].first; bytes = n->wreg[index].second; }
-    else if (!n->f16s || f16s_weight_buffer(n->f16s, index - n32, &p, &bytes)) return AF_NET_ERR_ARG;
+    if (index < kWeightBufs) { p = n->w[index]; bytes = weight_count(index, n->HW) * sizeof(float); }
+    else if (!n->f16s || f16s_weight_buffer(n->f16s, index - kWeightBufs, &p, &bytes)) return AF_NET_ERR_ARG;
     if (!host_out) return (int64_t)bytes;
     if (cap_bytes < (int64_t)bytes) return AF_NET_ERR_ARG;
     NET_HIP_OK(hipSetDevice(n->device));
@@ -904,10 +899,10 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
     float* policy = policy_all + (size_t)b0 * HW;
     float* value = value_all + b0;
     const size_t po = (size_t)b0 * PP;
-    float* f0 = n->f0 + po * 32;
+    float* f0 = n->act[kF0] + po * 32;
     float* g[5];
     float* o[5];
-    for (int i = 0; i < 5; ++i) { g[i] = n->g[i] + po * kBlocks[i].cout; o[i] = n->o[i] + po * kBlocks[i].cout; }
+    for (int i = 0; i < 5; ++i) { g[i] = n->act[kG + 2 * i] + po * kBlocks[i].cout; o[i] = n->act[kO + 2 * i] + po * kBlocks[i].cout; }
     const bool split16 = g_wino == 5 && n->f16s != nullptr;     // (board sizes without the split-operand path run the fp32 Winograd path)
     const bool fhead = split16 && g_fhead;                 // heads fused into the split-operand path
     F16sPlan plan = {};
@@ -918,7 +913,7 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
         if (plan.form != kF16sBranches) return f16s_forward(n->f16s, plan, st, planes, value, policy) ? AF_NET_ERR_HIP : AF_NET_OK;
         if (f16s_trunk(n->f16s, plan, st, planes)) return AF_NET_ERR_HIP;
     } else {
-        hipLaunchKernelGGL(af_stem_conv, dim3(batch), dim3(256), 0, st, planes, n->stem_w, n->stem_b, f0, S, WP, PP);
+        hipLaunchKernelGGL(af_stem_conv, dim3(batch), dim3(256), 0, st, planes, n->w[kStemW], n->w[kStemB], f0, S, WP, PP);
     }
     const float* block_in[5] = {f0, o[0], o[1], o[1], o[3]};
     // the value branch (block3 + head) only depends on the trunk output o[1]: it runs on a side stream,
@@ -943,13 +938,13 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
             if (i == 4 && f16s_policy_branch(n->f16s, plan, st, o[4], WP, PP, policy)) return AF_NET_ERR_HIP;
         } else {
             // conv1 3x3 + ELU (network.py:54); conv2 3x3 (+) 1x1 projection, add, ELU (network.py:53,55,56)
-            launch_wino(st, n, batch, block_in[i], n->wino1_u[i], b.cin, nullptr, nullptr, 0, n->conv1_b[i], g[i], b.cout);
-            launch_wino(st, n, batch, g[i], n->wino2_u[i], b.cout, block_in[i], n->winor_u[i], b.cin, n->sum_b[i], o[i], b.cout);
+            launch_wino(st, n, batch, block_in[i], n->w[kWino1 + i], b.cin, nullptr, nullptr, 0, n->w[kConv1B + i], g[i], b.cout);
+            launch_wino(st, n, batch, g[i], n->w[kWino2 + i], b.cout, block_in[i], n->w[kWinoR + i], b.cin, n->w[kSumB + i], o[i], b.cout);
         }
         if (i == 2) {
             if (!fhead)
-            hipLaunchKernelGGL(af_value_head, dim3((batch + VPB - 1) / VPB), dim3(256), 0, st, o[2], n->vc_w, n->vc_b, n->v1_w, n->v1_b,
-                               n->v2_w, n->v2_b, value, batch, S, WP, PP);
+            hipLaunchKernelGGL(af_value_head, dim3((batch + VPB - 1) / VPB), dim3(256), 0, st, o[2], n->w[kVcW], n->w[kVcB], n->w[kV1W], n->w[kV1B],
+                               n->w[kV2W], n->w[kV2B], value, batch, S, WP, PP);
             if (vs != st_main) NET_HIP_OK(hipEventRecord(n->ev_value, vs));
         }
     }
@@ -958,16 +953,16 @@ static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int
     } else if (HW <= 128 && g_phead) {
         const int K = 16 * HW, KS = K + ((2 - K % 32) + 32) % 32;
         const size_t lds = (size_t)16 * KS * 4;
-        hipLaunchKernelGGL(af_policy_head_mfma, dim3((batch + 15) / 16), dim3(256), lds, st, o[4], n->pc_w, n->pc_b, n->pf_w,
-                           n->pf_b, policy, batch, S, WP, PP);
+        hipLaunchKernelGGL(af_policy_head_mfma, dim3((batch + 15) / 16), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
+                           n->w[kPfB], policy, batch, S, WP, PP);
     } else if (HW <= 128) {
         const size_t lds = ((size_t)16 * HW * 8 + 512 + 32) * 4;
-        hipLaunchKernelGGL((af_policy_head<8>), dim3((batch + 7) / 8), dim3(256), lds, st, o[4], n->pc_w, n->pc_b, n->pf_w,
-                           n->pf_b, policy, batch, S, WP, PP);
+        hipLaunchKernelGGL((af_policy_head<8>), dim3((batch + 7) / 8), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
+                           n->w[kPfB], policy, batch, S, WP, PP);
     } else {
         const size_t lds = ((size_t)16 * HW * 4 + 512 + 16) * 4;
-        hipLaunchKernelGGL((af_policy_head<4>), dim3((batch + 3) / 4), dim3(256), lds, st, o[4], n->pc_w, n->pc_b, n->pf_w,
-                           n->pf_b, policy, batch, S, WP, PP);
+        hipLaunchKernelGGL((af_policy_head<4>), dim3((batch + 3) / 4), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
+                           n->w[kPfB], policy, batch, S, WP, PP);
     }
     if (vs != st) NET_HIP_OK(hipStreamWaitEvent(st, n->ev_value, 0));
     NET_HIP_OK(hipGetLastError());

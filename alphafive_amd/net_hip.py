@@ -66,9 +66,9 @@ class HipNet(object):
         self.value = torch.empty((max_batch,), dtype=torch.float32, device=self.device)
 
     def load(self, variables):
-        """(Re)load a weight set from host arrays: af_net_set_variable for every tensor, then af_net_finalize re-creates the handle's
-        buffers, uploads the tensors as they are and packs them on the device (the kernels of load_device); done when it returns."""
-        torch.cuda.synchronize(self.device)             # no forward may still be reading the old packed weights
+        """(Re)load a weight set from host arrays: af_net_set_variable copies every tensor into the handle's host image, then
+        af_net_finalize waits for the device (forwards in flight still read the old packed weights), uploads the image and packs it
+        in place into the buffers af_net_create made (the kernels of load_device); done when it returns.  Nothing is allocated."""
         for name, arr in variables.items():
             a = np.ascontiguousarray(arr, np.float32)
             _check(lib().af_net_set_variable(self._h, name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), a.size),

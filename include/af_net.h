@@ -28,15 +28,20 @@ typedef struct af_net af_net;
 #define AF_NET_ERR_NAME  (-3)   /* unknown variable name or wrong element count */
 #define AF_NET_ERR_STATE (-4)   /* forward before finalize / missing variables */
 
-/* board_size S (3..16); max_batch = largest batch af_net_forward will be called with. */
+/* board_size S (3..16); max_batch = largest batch af_net_forward will be called with.  Allocates everything the handle will ever own
+ * — weight, activation and staging buffers of both conv paths, its side stream and events — or frees what it made and returns
+ * AF_NET_ERR_HIP; no later call allocates or frees until af_net_destroy. */
 int af_net_create(int32_t board_size, int32_t max_batch, int32_t device, af_net** out);
 void af_net_destroy(af_net* n);
 
-/* Provide one variable (host pointer, fp32, TF layout) — e.g. "bone/block1_conv1/kernel". */
+/* Provide one variable (host pointer, fp32, TF layout) — e.g. "bone/block1_conv1/kernel": copied into the handle's host image of the
+ * variables at once.  af_net_forward returns AF_NET_ERR_STATE from here until the next af_net_finalize or af_net_update_device. */
 int af_net_set_variable(af_net* n, const char* tf_name, const float* host_data, int64_t count);
-/* Call after all 42 variables are set: (re-)creates the handle's device buffers, uploads the variables to a temporary device buffer
- * and packs them there with the kernels of af_net_update_device (k-pair-major streams and split fp16 fragments for the MFMA
- * kernels).  The packing has finished and the temporary buffer is gone when it returns. */
+/* Call after all 42 variables are set (AF_NET_ERR_STATE otherwise): waits for the device — forwards in flight on any stream still read
+ * the packed weights, so the caller need not wait for them itself —, uploads the host image to the handle's staging area in one copy
+ * and packs it in place with the kernels of af_net_update_device (k-pair-major streams and split fp16 fragments for the MFMA
+ * kernels).  The packing has finished when it returns: a forward on any stream finds the new weights.  A graph captured over the
+ * handle before the call does not: the split-operand kernels take their scales by value. */
 int af_net_finalize(af_net* n);
 
 /* Weight hand-over without the host: all 42 variables at once, from DEVICE memory (fp32, TF layout, same names / counts as

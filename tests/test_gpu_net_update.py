@@ -83,12 +83,12 @@ def _dev(v):
     return {k: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda() for k, a in v.items()}
 
 
-def _pair(S, V, max_batch, check_changed=False):
+def _pair(S, V, max_batch, check_changed=False, other=None):
     """A: V through the host path.  B: other weights through the host path, then V through the device update."""
     import torch
     from alphafive_amd import net_hip
     A = net_hip.HipNet(V, S, max_batch, "cuda")
-    B = net_hip.HipNet(_random_weights(S, 99), S, max_batch, "cuda")
+    B = net_hip.HipNet(other if other is not None else _random_weights(S, 99), S, max_batch, "cuda")
     before = B.debug_weights() if check_changed else None
     src = _dev(V)
     ver = B.weights_version()
@@ -120,19 +120,28 @@ CASES = [(11, "ckpt"), (11, "random"), (15, "random"), (9, "random")]
 @pytest.mark.parametrize("variant", ["plain", "scaled", "zero"])
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-%s" % (c[0], c[0], c[1]))
 def test_device_update_packs_the_bytes_of_the_host_path(case, variant):
+    """A (host load), B (device update over other weights) and C (a second host load over other weights) hold the same, recorded
+    bytes.  af_net_finalize packs in place into the buffers af_net_create made: C is where a byte that no packer rewrites would show."""
+    from alphafive_amd import net_hip
     S = case[0]
     V = _variant(_weights(case), variant)
-    A, B, _ = _pair(S, V, 8, check_changed=True)
+    other = _random_weights(S, 99)
+    A, B, _ = _pair(S, V, 8, check_changed=True, other=other)
+    C = net_hip.HipNet(other, S, 8, "cuda")
     key = "%dx%d-%s-%s" % (S, S, case[1], variant)
     try:
+        C.load(V)
         scales = _assert_same_state(A, B, S)
+        _assert_same_state(A, C, S)
         _assert_recorded_state(A, key, "A (af_net_finalize)")
         _assert_recorded_state(B, key, "B (af_net_update_device)")
+        _assert_recorded_state(C, key, "C (af_net_finalize over other weights)")
         if variant == "zero" and scales.size:
             assert scales[1 + 5] == 1.0         # layer 5 = value/block3 conv2, its projection produced separately: an all-zero group
     finally:
         A.close()
         B.close()
+        C.close()
 
 
 def _forward(h, xt):
@@ -204,7 +213,7 @@ def test_update_is_ordered_on_its_stream_between_two_forwards():
 def test_host_load_after_a_device_update_restores_the_first_weights_for_any_stream():
     """load(V0) -> load_device(V1) -> load(V0) on one handle: the recorded bytes of V0 again and V0's forward bit for bit — also for
     a forward queued on a fresh non-default stream right behind load(), with no wait of the test's own: af_net_finalize packs
-    with kernels out of a staging buffer it has freed by then, and has to have finished them before it returns."""
+    with kernels on the null stream out of the handle's staging area, and has to have finished them before it returns."""
     import torch
     from alphafive_amd import net_hip
     S, nb = 11, 8
@@ -235,6 +244,40 @@ def test_host_load_after_a_device_update_restores_the_first_weights_for_any_stre
     finally:
         H.close()
         H0.close()
+
+
+def test_host_load_waits_for_the_forwards_in_flight():
+    """Four forwards with V0 queued on a fresh non-default stream, load(V1) from the host at once — no wait of the test's own —,
+    then a fifth forward: the first four are V0's bit for bit, the fifth V1's.  af_net_finalize rewrites the packed weights in
+    place, so it is the library that has to wait for what still reads them."""
+    import torch
+    from alphafive_amd import net_hip
+    S, nb = 11, 64
+    V0, V1 = _weights((11, "ckpt")), _random_weights(11, 5)
+    H0, H1 = net_hip.HipNet(V0, S, nb, "cuda"), net_hip.HipNet(V1, S, nb, "cuda")
+    H = net_hip.HipNet(V0, S, nb, "cuda")
+    try:
+        x = torch.from_numpy(_positions(S, nb, seed=4)).cuda()
+        refs = [_forward(h, x) for h in (H0, H1)]
+        outs = [(torch.zeros(nb, S * S, device="cuda"), torch.zeros(nb, device="cuda")) for _ in range(5)]
+        s = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            for out in outs[:4]:
+                H.bind_outputs(*out)
+                H(x)
+            H.load(V1)
+            H.bind_outputs(*outs[4])
+            H(x)
+        s.synchronize()
+        for i, (p, v) in enumerate(outs):
+            pr, vr = refs[i // 4]
+            assert np.array_equal(p.cpu().numpy().view(np.uint32), pr.view(np.uint32)), i
+            assert np.array_equal(v.cpu().numpy().view(np.uint32), vr.view(np.uint32)), i
+        assert not np.array_equal(refs[0][1], refs[1][1])
+    finally:
+        for h in (H, H0, H1):
+            h.close()
 
 
 def _synthetic_batch(rng, S, n=64):

@@ -4,7 +4,11 @@ ended by a device synchronise (host clock around it).  Two paths, alternated in 
   (a) host    net.set_variables(trainer.variables())                       — 42 copies to the host, host re-pack, af_net_finalize
   (b) device  net.set_variables_device(trainer.device_variables())         — device snapshot, af_net_update_device in place
 Between hand-offs the trainer takes one optimiser step (outside the timed window), so every hand-off carries new weights.
-Prints one JSON line with medians and interquartile ranges in ms.  Env: REPEATS (20, at least 20 of each), B (4096)."""
+Prints one JSON line with medians and interquartile ranges in ms.  Env: REPEATS (20, at least 20 of each), B (4096).
+
+`probe_weight_handoff.py host_load`: HipNet.load(variables) alone on one handle of that size — one warm-up load, then five, each between
+two device synchronisations (host clock) — as one JSON line.  AF_NET_LIB selects the library, so a parent build and a change run
+back to back in separate processes."""
 import json
 import os
 import sys
@@ -21,6 +25,30 @@ from alphafive_amd.train import Trainer                                # noqa: E
 S = 11
 B, REPEATS = int(os.environ.get("B", 4096)), max(20, int(os.environ.get("REPEATS", 20)))
 dev = torch.device("cuda", 0)
+
+
+def host_load():
+    from alphafive_amd import net_hip
+    with np.load(os.path.join(REPO, "tests", "golden", "alphaFive-6960.weights.npz")) as z:
+        sets = [{k: np.ascontiguousarray(z[k], np.float32) for k in z.files}]
+    sets.append({k: (a * np.float32(0.5)) for k, a in sets[0].items()})        # every load carries other weights than the one before
+    h = net_hip.HipNet(sets[0], S, B, dev)
+    ms = []
+    for i in range(6):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.load(sets[(i + 1) % 2])
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    h.close()
+    print(json.dumps({"probe": "host_load", "library": os.path.basename(os.path.dirname(net_hip._LIBPATH)) + "/" + os.path.basename(net_hip._LIBPATH),
+                      "board": S, "max_batch": B, "warmup_ms": ms[0], "samples_ms": ms[1:], "median_ms": float(np.median(ms[1:]))}))
+
+
+if sys.argv[1:] == ["host_load"]:
+    host_load()
+    sys.exit(0)
+
 net = ResNet(S, device=dev)
 net.load_npz(os.path.join(REPO, "tests", "golden", "alphaFive-6960.weights.npz"))
 trainer = Trainer(net.variables, S, device=dev)
