@@ -79,26 +79,84 @@ def loss_terms(params, boards, distrib, winner, weights, forward=forward_train):
 class Trainer(object):
     """Holds the variables as torch parameters (TF layout/names) + TF-style Adam slots.  The update of the 42 variables is nine
     multi-tensor launches instead of ~210 per-variable ones (at the reference's batch of 512 the step is launch-bound:
-    7.4 -> 6.0 ms, tools/probe_train_step.py); step(..., metrics=False) returns None and never waits for the device."""
+    7.4 -> 6.0 ms, tools/probe_train_step.py); step(..., metrics=False) returns None and never waits for the device.
 
-    def __init__(self, variables, board_size, device=None, beta1=0.9, beta2=0.999, eps=1e-8, forward=None, shapes=None):
+    fused=True (a CUDA/ROCm device only) takes everything but the network itself out of PyTorch: the loss head with its gradient,
+    Adam with the L2 gradient and the L2 sum, and the logged scalars are three HIP launches (train_hip, include/af_train.h)
+    around one torch.autograd.grad through the convolutions and dense layers.  `total`'s graph — the 21 per-variable L2 sums
+    among it — is never built.  The variables, `m` and `v` then live in one flat buffer each; params / m / v are views into
+    them under the same names and shapes, so everything below reads and writes them as before."""
+
+    def __init__(self, variables, board_size, device=None, beta1=0.9, beta2=0.999, eps=1e-8, forward=None, shapes=None,
+                 fused=False):
         """`forward` / `shapes`: the differentiable forward and the {name: shape} table of the net to train; by default the
         42-variable net's (forward_train, network.variable_shapes).  DeepResNet: forward_train_deep, net.variable_shapes()."""
         self.board_size = board_size
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.forward = forward if forward is not None else forward_train
+        self.fused = bool(fused)
+        if self.fused and self.device.type != "cuda":
+            raise ValueError("Trainer(fused=True) runs HIP kernels (libaf_train.so) and needs a CUDA/ROCm device, not %r: "
+                             "there is no host version of them to fall back to" % str(self.device))
         shapes = shapes if shapes is not None else variable_shapes(board_size)
+        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        self.t = 0
+        if self.fused:
+            self._init_fused(variables, shapes)
+            return
         self.params = {k: torch.tensor(np.asarray(variables[k], np.float32), device=self.device, requires_grad=True)
                        for k in shapes}
         self.m = {k: torch.zeros_like(p) for k, p in self.params.items()}
         self.v = {k: torch.zeros_like(p) for k, p in self.params.items()}
-        self.beta1, self.beta2, self.eps = beta1, beta2, eps
-        self.t = 0
         self._lr_t = torch.zeros((), dtype=torch.float32, device=self.device)
+
+    def _init_fused(self, variables, shapes):
+        """One flat buffer each for the variables, m and v; params / m / v are views into them (the parameters leaves that
+        require grad: a view of a tensor that does not is a leaf).  The Adam table is built once: these pointers never move."""
+        from . import train_hip
+        train_hip.lib()                                     # a missing library is an error here, not at the first step
+        sizes = {k: int(np.prod(shp, dtype=np.int64)) for k, shp in shapes.items()}
+        total = sum(sizes.values())
+        host = np.empty(total, np.float32)
+        views, off = {}, 0
+        for k, shp in shapes.items():
+            a = np.asarray(variables[k], np.float32)
+            if tuple(a.shape) != tuple(shp):
+                raise ValueError("variable %s has shape %s, expected %s" % (k, a.shape, tuple(shp)))
+            host[off:off + sizes[k]] = a.reshape(-1)
+            views[k] = (off, off + sizes[k], tuple(shp))
+            off += sizes[k]
+        self._flat = dict(params=torch.from_numpy(host).to(self.device),
+                          m=torch.zeros(total, dtype=torch.float32, device=self.device),
+                          v=torch.zeros(total, dtype=torch.float32, device=self.device))
+        cut = lambda flat: {k: flat[a:b].view(shp) for k, (a, b, shp) in views.items()}
+        self.params = {k: p.requires_grad_(True) for k, p in cut(self._flat["params"]).items()}
+        self.m, self.v = cut(self._flat["m"]), cut(self._flat["v"])
+        names = list(shapes)
+        self._table = train_hip.VarTable([self.params[k] for k in names], [self.m[k] for k in names],
+                                         [self.v[k] for k in names], ["bias" not in k and "bn" not in k for k in names])
+        self._l2_partials = torch.zeros(max(1, self._table.n_partials), dtype=torch.float32, device=self.device)
+        self._lr_t = 0.0                                    # a kernel argument on this path, not a device scalar
+
+    def _update_fused(self, batch):
+        """forward -> loss head (d total / d logits, d total / d value without the L2 term) -> autograd through the network ->
+        Adam (adds the L2 gradient l2_coef * p itself, sums p^2 on the way) -> the four scalars, all on the device."""
+        from . import train_hip
+        boards, distrib, winner, weights = batch
+        ps = list(self.params.values())
+        logits, value = self.forward(self.params, boards)
+        dlogits, dvalue, rows = train_hip.loss_head(logits, value, distrib.contiguous(), winner.contiguous(),
+                                                    weights.contiguous())
+        self._table.set_grads(torch.autograd.grad([logits, value], ps, [dlogits, dvalue]))
+        n = train_hip.adam(self._table, self._lr_t, self.beta1, self.beta2, self.eps, train_hip.L2_COEF, self._l2_partials)
+        terms = train_hip.finalize(rows, self._l2_partials, n, train_hip.L2_COEF)
+        return dict(total=terms[0], cross_entropy=terms[1], value_loss=terms[2], entropy=terms[3])
 
     def _update(self, batch):
         """loss -> gradients -> Adam (tf.train.AdamOptimizer: lr_t folds the bias corrections, eps is added to sqrt(v)).
         Same arithmetic order as the per-variable loop it replaces: p -= (lr_t * m) / (sqrt(v) + eps)."""
+        if self.fused:
+            return self._update_fused(batch)
         terms = loss_terms(self.params, *batch, forward=self.forward)
         ps = list(self.params.values())
         grads = list(torch.autograd.grad(terms["total"], ps))
@@ -123,7 +181,11 @@ class Trainer(object):
             return torch.as_tensor(np.asarray(a, np.float32), device=self.device)
         batch = (to(boards), to(policies), to(values), to(weights))
         self.t += 1
-        self._lr_t.fill_(float(lr * np.sqrt(1.0 - self.beta2 ** self.t) / (1.0 - self.beta1 ** self.t)))
+        lr_t = float(lr * np.sqrt(1.0 - self.beta2 ** self.t) / (1.0 - self.beta1 ** self.t))
+        if self.fused:
+            self._lr_t = lr_t
+        else:
+            self._lr_t.fill_(lr_t)
         terms = self._update(batch)
         return {k: float(v) for k, v in terms.items()} if metrics else None
 
