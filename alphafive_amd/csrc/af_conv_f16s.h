@@ -1,12 +1,29 @@
 // af_conv_f16s.h — internal interface (inside libaf_net.so) between af_net.hip and af_conv_f16s.hip: the fp16
-// split-operand convolution path of the network (11x11 and 15x15 boards).  Not part of the C ABI (include/af_net.h is).
+// split-operand convolution path of the network (11x11 and 15x15 boards), and the table of the network's blocks and variables that
+// both read.  Not part of the C ABI (include/af_net.h is).
 #ifndef AF_CONV_F16S_H
 #define AF_CONV_F16S_H
 
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <string>
+// ---- the network's tensors, stated once for both conv paths: five residual blocks and 42 variables ----
+#define AF_NET_BLOCKS(X) X("bone/block1", 32, 64) X("bone/block2", 64, 128) X("value/block3", 128, 32) X("policy/block4", 128, 64) X("policy/block5", 64, 32)
+struct NetBlock { const char* name; int cin, cout; };
+#define AF_BLOCK_ROW(name, cin, cout) {name, cin, cout},
+constexpr NetBlock kBlocks[5] = {AF_NET_BLOCKS(AF_BLOCK_ROW)};
+// The variables in the order of the staging area (and of every `const float* const* src` of the packers): the stem's two, the ten of
+// the heads, six per block: src[var(b, kC1K)] is block b's conv1 kernel.
+enum { kVarStemK, kVarStemB, kVarHeads, kVarVcK = kVarHeads, kVarVcB, kVarV1K, kVarV1B, kVarV2K, kVarV2B, kVarPcK, kVarPcB, kVarPfK, kVarPfB,
+       kVarBlocks, kVars = kVarBlocks + 6 * 5, kC1K = 0, kC1B, kC2K, kC2B, kResK, kResB };
+constexpr int var(int block, int which) { return kVarBlocks + 6 * block + which; }
+struct NetVar { const char* name; int c0, c1, c2; };      // TF name; element count = c0 + c1 * HW + c2 * HW * HW (HW = S*S)
+#define AF_BLOCK_VARS(name, cin, cout) {name "_conv1/kernel", 9 * cin * cout}, {name "_conv1/bias", cout}, {name "_conv2/kernel", 9 * cout * cout}, \
+                                       {name "_conv2/bias", cout}, {name "_res/kernel", cin * cout}, {name "_res/bias", cout},
+constexpr NetVar kNetVars[kVars] = {
+    {"bone/conv1/kernel", 75 * 32}, {"bone/conv1/bias", 32}, {"value/conv/kernel", 32 * 4}, {"value/conv/bias", 4},
+    {"value/fc1/kernel", 0, 4 * 64}, {"value/fc1/bias", 64}, {"value/fc2/kernel", 64}, {"value/fc2/bias", 1},
+    {"policy/conv/kernel", 32 * 16}, {"policy/conv/bias", 16}, {"policy/fc/kernel", 0, 0, 16}, {"policy/fc/bias", 0, 1},
+    AF_NET_BLOCKS(AF_BLOCK_VARS)};
 
 struct f16s_net;
 
@@ -59,15 +76,14 @@ int f16s_read_activation(f16s_net* n, int which, int batch, float* host);
 
 // ---- weight packing, from device memory and in place: the one packer of this path (af_net_finalize over the variables it staged,
 // af_net_update_device over the caller's tensors) ----
-// name -> fp32 TF-layout tensor in DEVICE memory, all 42 variables (af_net.hip has checked names and counts)
-typedef std::map<std::string, const float*> f16s_dev_vars;
+// src: the 42 variables as fp32 TF-layout tensors in DEVICE memory, in kNetVars' order (af_net.hip has checked names and counts)
 constexpr int kF16sScaleGroups = 20;       // stem | per block: conv1, conv2 (+ folded projection), produced projection | 2 head convs | value/fc1 | policy/fc
 // max|w| of every scale group -> max_dev[kF16sScaleGroups] (device; NaN elements do not count), asynchronous on st
-int f16s_update_absmax(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, float* max_dev);
-// pack every weight-derived buffer of the split-operand path in place from D, each scale group with the power-of-two scale its
+int f16s_update_absmax(f16s_net* n, hipStream_t st, const float* const* src, float* max_dev);
+// pack every weight-derived buffer of the split-operand path in place from src, each scale group with the power-of-two scale its
 // max_host[group] picks, asynchronous on st, and store the new inverse scales in the handle; max_host = what f16s_update_absmax
 // produced, already on the host
-int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const float* max_host);
+int f16s_update_pack(f16s_net* n, hipStream_t st, const float* const* src, const float* max_host);
 // weight-derived device buffers in a fixed order (af_net_debug_weights): 0 on success, -1 past the last one
 int f16s_weight_buffer(const f16s_net* n, int index, const void** ptr, size_t* bytes);
 int f16s_scales(const f16s_net* n, float* out, int cap);           // the 25 inverse scales (af_net_debug_scales); returns how many

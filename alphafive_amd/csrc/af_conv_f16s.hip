@@ -31,8 +31,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <map>
-#include <string>
 #include <vector>
 
 #include "af_conv_f16s.h"
@@ -1765,7 +1763,10 @@ constexpr LayerCfg kLayers[10] = {
     {128, 64, 0, 2, 2, 1, 1, 0, false},  {64, 64, 128, 2, 2, 1, 1, 0, true},      // policy/block4
     {64, 32, 0, 1, 1, 4, 1, 1, true},    {32, 32, 0, 1, 1, 4, 1, 2, true},        // policy/block5
 };
-const char* const kBlockNames[5] = {"bone/block1", "bone/block2", "value/block3", "policy/block4", "policy/block5"};
+constexpr bool layers_of_block(int b) {       // conv1 cin -> cout, conv2 cout -> cout
+    return kLayers[2 * b].cin == kBlocks[b].cin && kLayers[2 * b].cout == kBlocks[b].cout && kLayers[2 * b + 1].cin == kBlocks[b].cout && kLayers[2 * b + 1].cout == kBlocks[b].cout;
+}
+static_assert(layers_of_block(0) && layers_of_block(1) && layers_of_block(2) && layers_of_block(3) && layers_of_block(4), "kLayers against kBlocks (af_conv_f16s.h)");
 template <int LI> constexpr int kHeadOf = LI == 4 || LI == 5 ? 1 : LI == 8 || LI == 9 ? 2 : 0;   // the head blocks 3 / 5 can fuse: 1 value, 2 policy
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of kernel K, set once: the attribute belongs to the (function, device) pair, so each K has
@@ -1975,7 +1976,6 @@ int f16s_reset_roles(f16s_net* n) {
     return 0;
 }
 
-
 // ------------------------------------------------ weight packing (device kernels) ------------------------------------------------
 // The only packers of this path: af_net_finalize (variables staged from the host) and af_net_update_device (variables already on
 // the device) both end in f16s_update_absmax + f16s_update_pack.  One thread per fragment row (8 halves hi + 8 halves lo = two
@@ -2116,30 +2116,29 @@ int upd_launch_copies(hipStream_t st, const UpdCopy* d, int count) {
 
 // scale groups, in order: 0 stem; 1 + 3b conv1 of block b, 2 + 3b conv2 (+ the folded projection), 3 + 3b the produced projection
 // (computed for every block, used by blocks 3 and 5); 16 / 17 value / policy head conv; 18 value/fc1; 19 policy/fc
-int f16s_update_absmax(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, float* max_dev) {
+int f16s_update_absmax(f16s_net* n, hipStream_t st, const float* const* src, float* max_dev) {
     const int npix = n->S * n->S;
     MaxTable T = {};
-    T.g[0] = {D.at("bone/conv1/kernel"), nullptr, 75 * 32, 0};
+    T.g[0] = {src[kVarStemK], nullptr, 75 * 32, 0};
     for (int b = 0; b < 5; ++b) {
-        const std::string s = kBlockNames[b];
         const LayerCfg &L1 = kLayers[2 * b], &L2 = kLayers[2 * b + 1];
-        const float* kr = D.at(s + "_res/kernel");
+        const float* kr = src[var(b, kResK)];
         const int nr = L1.cin * L2.cout;
-        T.g[1 + 3 * b] = {D.at(s + "_conv1/kernel"), nullptr, 9 * L1.cin * L1.cout, 0};
-        T.g[2 + 3 * b] = {D.at(s + "_conv2/kernel"), kr, 9 * L2.cin * L2.cout, L1.pj == 1 ? 0 : nr};
+        T.g[1 + 3 * b] = {src[var(b, kC1K)], nullptr, 9 * L1.cin * L1.cout, 0};
+        T.g[2 + 3 * b] = {src[var(b, kC2K)], kr, 9 * L2.cin * L2.cout, L1.pj == 1 ? 0 : nr};
         T.g[3 + 3 * b] = {kr, nullptr, nr, 0};
     }
-    T.g[16] = {D.at("value/conv/kernel"), nullptr, 32 * 4, 0};
-    T.g[17] = {D.at("policy/conv/kernel"), nullptr, 32 * 16, 0};
-    T.g[18] = {D.at("value/fc1/kernel"), nullptr, 4 * npix * 64, 0};
-    T.g[19] = {D.at("policy/fc/kernel"), nullptr, 16 * npix * npix, 0};
+    T.g[16] = {src[kVarVcK], nullptr, 32 * 4, 0};
+    T.g[17] = {src[kVarPcK], nullptr, 32 * 16, 0};
+    T.g[18] = {src[kVarV1K], nullptr, 4 * npix * 64, 0};
+    T.g[19] = {src[kVarPfK], nullptr, 16 * npix * npix, 0};
     FS_HIP_OK(hipMemsetAsync(max_dev, 0, kF16sScaleGroups * sizeof(float), st));
     hipLaunchKernelGGL(af_update_absmax, dim3(kMaxBlocks, kF16sScaleGroups), dim3(256), 0, st, T, max_dev);
     FS_HIP_OK(hipGetLastError());
     return 0;
 }
 
-int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const float* max_host) {
+int f16s_update_pack(f16s_net* n, hipStream_t st, const float* const* src, const float* max_host) {
     const int npix = n->S * n->S;
     float sc[kF16sScaleGroups];
     for (int g = 0; g < kF16sScaleGroups; ++g) sc[g] = pick_scale(max_host[g]);
@@ -2151,29 +2150,28 @@ int f16s_update_pack(f16s_net* n, hipStream_t st, const f16s_dev_vars& D, const 
     UpdCopy C[kMaxCopies];
     int ncp = 0;
     auto copy = [&](float* dst, const float* a, const float* b, int n_dst, int n_src, int sum) { C[ncp++] = UpdCopy{dst, a, b, n_dst, n_src, sum}; };
-    frag(n->stem_wm, D.at("bone/conv1/kernel"), nullptr, sc[0], FK_STEM, kStemFrags, 0, 0, 0, 1, 0);
-    copy(n->stem_w, D.at("bone/conv1/kernel"), nullptr, 75 * 32, 75 * 32, 0);
-    copy(n->stem_b, D.at("bone/conv1/bias"), nullptr, 32, 32, 0);
+    frag(n->stem_wm, src[kVarStemK], nullptr, sc[0], FK_STEM, kStemFrags, 0, 0, 0, 1, 0);
+    copy(n->stem_w, src[kVarStemK], nullptr, 75 * 32, 75 * 32, 0);
+    copy(n->stem_b, src[kVarStemB], nullptr, 32, 32, 0);
     for (int b = 0; b < 5; ++b) {
-        const std::string s = kBlockNames[b];
         const LayerCfg &L1 = kLayers[2 * b], &L2 = kLayers[2 * b + 1];
-        const float *k1 = D.at(s + "_conv1/kernel"), *k2 = D.at(s + "_conv2/kernel"), *kr = D.at(s + "_res/kernel");
+        const float *k1 = src[var(b, kC1K)], *k2 = src[var(b, kC2K)], *kr = src[var(b, kResK)];
         frag(n->w[2 * b], k1, nullptr, sc[1 + 3 * b], FK_LAYER, layer_frags(L1), L1.cin, L1.cout, L1.pcin, L1.KS, 0);
         frag(n->w[2 * b + 1], k2, kr, sc[2 + 3 * b], FK_LAYER, layer_frags(L2), L2.cin, L2.cout, L2.pcin, L2.KS, 0);
         if (L1.pj == 1) frag(n->pw[2 * b], nullptr, kr, sc[3 + 3 * b], FK_LAYER, proj_frags(L1, L2.cout), 0, L2.cout, L1.cin, L1.KS, 0);
-        copy(n->bias[2 * b], D.at(s + "_conv1/bias"), nullptr, L1.cout, L1.cout, 0);
-        copy(n->bias[2 * b + 1], D.at(s + "_conv2/bias"), D.at(s + "_res/bias"), L2.cout, L2.cout, 1);
+        copy(n->bias[2 * b], src[var(b, kC1B)], nullptr, L1.cout, L1.cout, 0);
+        copy(n->bias[2 * b + 1], src[var(b, kC2B)], src[var(b, kResB)], L2.cout, L2.cout, 1);
     }
-    frag(n->hcw[0], D.at("value/conv/kernel"), nullptr, sc[16], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 4);
-    frag(n->hcw[1], D.at("policy/conv/kernel"), nullptr, sc[17], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 16);
-    frag(n->hfw[0], D.at("value/fc1/kernel"), nullptr, sc[18], FK_VFC, vfc_frags(npix), 0, 0, 0, 1, 0);
-    frag(n->hfw[1], D.at("policy/fc/kernel"), nullptr, sc[19], FK_PFC, pfc_frags(npix), 0, 0, 0, 1, 0);
-    copy(n->hcb[0], D.at("value/conv/bias"), nullptr, 16, 4, 0);
-    copy(n->hcb[1], D.at("policy/conv/bias"), nullptr, 16, 16, 0);
-    copy(n->hfb[0], D.at("value/fc1/bias"), nullptr, 64, 64, 0);
-    copy(n->hfb[1], D.at("policy/fc/bias"), nullptr, npix, npix, 0);
-    copy(n->v2w, D.at("value/fc2/kernel"), nullptr, 64, 64, 0);
-    copy(n->v2b, D.at("value/fc2/bias"), nullptr, 1, 1, 0);
+    frag(n->hcw[0], src[kVarVcK], nullptr, sc[16], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 4);
+    frag(n->hcw[1], src[kVarPcK], nullptr, sc[17], FK_HCONV, kHconvFrags, 0, 0, 0, 1, 16);
+    frag(n->hfw[0], src[kVarV1K], nullptr, sc[18], FK_VFC, vfc_frags(npix), 0, 0, 0, 1, 0);
+    frag(n->hfw[1], src[kVarPfK], nullptr, sc[19], FK_PFC, pfc_frags(npix), 0, 0, 0, 1, 0);
+    copy(n->hcb[0], src[kVarVcB], nullptr, 16, 4, 0);
+    copy(n->hcb[1], src[kVarPcB], nullptr, 16, 16, 0);
+    copy(n->hfb[0], src[kVarV1B], nullptr, 64, 64, 0);
+    copy(n->hfb[1], src[kVarPfB], nullptr, npix, npix, 0);
+    copy(n->v2w, src[kVarV2K], nullptr, 64, 64, 0);
+    copy(n->v2b, src[kVarV2B], nullptr, 1, 1, 0);
     hipLaunchKernelGGL(af_update_frags, dim3(kFragBlocks, nb), dim3(256), 0, st, T);
     FS_HIP_OK(hipGetLastError());
     if (upd_launch_copies(st, C, ncp)) return -2;
@@ -2299,6 +2297,7 @@ static int launch_policy_fc(const f16s_net* n, hipStream_t st, int batch, float*
     return with_geo(n, [&](auto g) {
         hipLaunchKernelGGL(af_policy_fc_f16s<decltype(g)>, dim3((batch + kPfPos - 1) / kPfPos), dim3(512), kPfLds, st, n->hx[1], n->hfw[1], n->hfb[1],
                            n->hf_inv[1], policy, batch);
+        FS_HIP_OK(hipGetLastError());
         return 0;
     });
 }
@@ -2306,13 +2305,14 @@ static int launch_policy_fc(const f16s_net* n, hipStream_t st, int batch, float*
 int f16s_trunk(f16s_net* n, const F16sPlan& p, hipStream_t st, const float* planes) {
     const int batch = p.batch;
     if (!n || batch < 1 || batch > n->max_batch) return -1;
-    with_geo(n, [&](auto g) {
+    int rc = with_geo(n, [&](auto g) {
         using G = decltype(g);
         if (p.valu_stem) hipLaunchKernelGGL(af_stem_f16s<G>, dim3(std::min(batch, 2048)), dim3(256), 0, st, planes, n->stem_w, n->stem_b, n->f0, batch);
         else hipLaunchKernelGGL(af_stem_mfma_f16s<G>, dim3(std::min(batch, 1024)), dim3(256), 0, st, planes, n->stem_wm, n->stem_b, n->stem_inv_scale, n->f0, batch);
+        FS_HIP_OK(hipGetLastError());
         return 0;
     });
-    int rc = launch_layer<0>(n, p, st, n->f0, nullptr, n->g[0]);
+    if (!rc) rc = launch_layer<0>(n, p, st, n->f0, nullptr, n->g[0]);
     if (!rc) rc = launch_layer<1>(n, p, st, n->g[0], n->f0, n->o[0]);
     if (!rc) rc = launch_layer<2>(n, p, st, n->o[0], nullptr, n->g[1]);
     if (!rc) rc = launch_layer<3>(n, p, st, n->g[1], n->o[0], n->o[1]);
@@ -2328,9 +2328,10 @@ int f16s_value_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o3,
         if (!rc) rc = launch_layer<5>(n, p, st, n->g[2], n->o[1], nullptr, o3, WP, PP);
     }
     if (!rc && p.heads)
-        with_geo(n, [&](auto g) {
+        rc = with_geo(n, [&](auto g) {
             hipLaunchKernelGGL(af_value_fc_f16s<decltype(g)>, dim3((p.batch + 31) / 32), dim3(128), 0, st, n->hx[0], n->hfw[0], n->hfb[0], n->v2w, n->v2b,
                                n->hf_inv[0], value, p.batch);
+            FS_HIP_OK(hipGetLastError());
             return 0;
         });
     return rc;
@@ -2345,7 +2346,7 @@ int f16s_policy_branch(f16s_net* n, const F16sPlan& p, hipStream_t st, float* o5
         if (!rc) rc = launch_layer<8>(n, p, st, n->o[3], nullptr, n->g[4]);
         if (!rc) rc = launch_layer<9>(n, p, st, n->g[4], n->o[3], nullptr, o5, WP, PP);
     }
-    if (!rc && p.heads) launch_policy_fc(n, st, p.batch, policy);
+    if (!rc && p.heads) rc = launch_policy_fc(n, st, p.batch, policy);
     return rc;
 }
 
@@ -2386,9 +2387,7 @@ static int paired_branches(f16s_net* n, const F16sPlan& p, hipStream_t st, float
     }
     FS_HIP_OK(hipGetLastError());
     const int rc = launch_block<G, 8>(st, block_args<8>(n, p, n->o[3]), n->ncu);
-    if (!rc) launch_policy_fc(n, st, batch, policy);
-    FS_HIP_OK(hipGetLastError());
-    return rc;
+    return rc ? rc : launch_policy_fc(n, st, batch, policy);
 }
 
 // kF16sRoles: the single-launch small-batch forward (af_small_forward_f16s) + the policy head's dense layer

@@ -21,8 +21,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <map>
-#include <string>
 #include <vector>
 
 #include "af_net.h"
@@ -589,32 +587,12 @@ __global__ __launch_bounds__(256) void af_policy_head_mfma(const float* __restri
 // ----------------------------------------------------------------------------------------------
 #define NET_HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[af_net] %s failed: %s\n", #x, hipGetErrorString(e_)); return AF_NET_ERR_HIP; } } while (0)
 
-struct Block { const char* name; int cin, cout; };
-static const Block kBlocks[5] = {{"bone/block1", 32, 64}, {"bone/block2", 64, 128}, {"value/block3", 128, 32},
-                                 {"policy/block4", 128, 64}, {"policy/block5", 64, 32}};
-
-// The 42 variables in the order of the staging area: the stem's two, the ten of the heads, six per block.
-// Element count = c0 + c1 * HW + c2 * HW * HW.
-enum { kVarHeads = 2, kVarBlocks = kVarHeads + 10, kVars = kVarBlocks + 6 * 5, kC1K = 0, kC1B, kC2K, kC2B, kResK, kResB };
-struct Var { std::string name; int c0, c1, c2; };
-static const std::vector<Var>& variables() {
-    static const std::vector<Var> table = [] {
-        std::vector<Var> t = {{"bone/conv1/kernel", 75 * 32}, {"bone/conv1/bias", 32}, {"value/conv/kernel", 32 * 4}, {"value/conv/bias", 4},
-                              {"value/fc1/kernel", 0, 4 * 64}, {"value/fc1/bias", 64}, {"value/fc2/kernel", 64}, {"value/fc2/bias", 1},
-                              {"policy/conv/kernel", 32 * 16}, {"policy/conv/bias", 16}, {"policy/fc/kernel", 0, 0, 16}, {"policy/fc/bias", 0, 1}};
-        for (const Block& b : kBlocks)
-            for (const Var& v : {Var{"_conv1/kernel", 9 * b.cin * b.cout}, Var{"_conv1/bias", b.cout}, Var{"_conv2/kernel", 9 * b.cout * b.cout},
-                                 Var{"_conv2/bias", b.cout}, Var{"_res/kernel", b.cin * b.cout}, Var{"_res/bias", b.cout}})
-                t.push_back({b.name + v.name, v.c0});
-        return t;
-    }();
-    return table;
-}
+// (the five blocks and the 42 variables: kBlocks, kNetVars and their indices in af_conv_f16s.h)
 static int var_index(const char* name) {
-    for (int i = 0; i < kVars; ++i) if (variables()[i].name == name) return i;
+    for (int i = 0; i < kVars; ++i) if (!strcmp(kNetVars[i].name, name)) return i;
     return -1;
 }
-static size_t var_count(int i, int HW) { const Var& v = variables()[i]; return v.c0 + (size_t)v.c1 * HW + (size_t)v.c2 * HW * HW; }
+static size_t var_count(int i, int HW) { const NetVar& v = kNetVars[i]; return v.c0 + (size_t)v.c1 * HW + (size_t)v.c2 * HW * HW; }
 static size_t var_offset(int i, int HW) {        // in floats; var_offset(kVars, HW) = the size of the staging area
     size_t at = 0;
     for (int k = 0; k < i; ++k) at += var_count(k, HW);
@@ -629,7 +607,7 @@ enum { kStemW, kStemB, kConv1B, kSumB = kConv1B + 5, kWino1 = kSumB + 5, kWino2 
 static size_t weight_count(int i, int HW) {
     if (i < kConv1B) return var_count(i, HW);
     if (i >= kHeadW) return var_count(kVarHeads + i - kHeadW, HW);
-    const Block& b = kBlocks[(i - kConv1B) % 5];
+    const NetBlock& b = kBlocks[(i - kConv1B) % 5];
     if (i < kWino1) return (b.cout + 31) / 32 * 32;          // biases are padded to a multiple of 32 couts
     if (i < kWino2) return (size_t)b.cin * b.cout * 16;
     return i < kWinoR ? (size_t)b.cout * b.cout * 16 : (size_t)b.cin * b.cout * 4;
@@ -697,33 +675,30 @@ __global__ __launch_bounds__(256) void af_update_wino(WinoPackTable T) {
 }
 
 // Packs every weight-derived buffer of the handle, in place, from the 42 fp32 TF-layout tensors src names in device memory
-// (variables()' order): the one packer behind af_net_finalize and af_net_update_device.  Asynchronous on st but for ONE wait: the
+// (kNetVars' order): the one packer behind af_net_finalize and af_net_update_device.  Asynchronous on st but for ONE wait: the
 // scales of the split-operand path need max|w| per group, reduced on the device and brought to the host as 80 bytes.
 static int pack_from_device(af_net* n, hipStream_t st, const float* const* src) {
     if (n->f16s) {
-        f16s_dev_vars D;
-        for (int i = 0; i < kVars; ++i) D[variables()[i].name] = src[i];
-        if (f16s_update_absmax(n->f16s, st, D, n->upd_max_dev)) return AF_NET_ERR_HIP;
+        if (f16s_update_absmax(n->f16s, st, src, n->upd_max_dev)) return AF_NET_ERR_HIP;
         NET_HIP_OK(hipMemcpyAsync(n->upd_max_host, n->upd_max_dev, kF16sScaleGroups * sizeof(float), hipMemcpyDeviceToHost, st));
         NET_HIP_OK(hipStreamSynchronize(st));
-        if (f16s_update_pack(n->f16s, st, D, n->upd_max_host)) return AF_NET_ERR_HIP;
+        if (f16s_update_pack(n->f16s, st, src, n->upd_max_host)) return AF_NET_ERR_HIP;
     }
     WinoPackTable W = {};
     UpdCopy C[22];
     int ncp = 0;
-    auto copy = [&](int buf, int var, const float* b, int sum) {
-        C[ncp++] = UpdCopy{n->w[buf], src[var], b, (int)weight_count(buf, n->HW), (int)var_count(var, n->HW), sum};
+    auto copy = [&](int buf, int v, const float* b, int sum) {
+        C[ncp++] = UpdCopy{n->w[buf], src[v], b, (int)weight_count(buf, n->HW), (int)var_count(v, n->HW), sum};
     };
-    copy(kStemW, 0, nullptr, 0); copy(kStemB, 1, nullptr, 0);
+    copy(kStemW, kVarStemK, nullptr, 0); copy(kStemB, kVarStemB, nullptr, 0);
     for (int i = 0; i < 5; ++i) {
-        const Block& b = kBlocks[i];
-        const int v = kVarBlocks + 6 * i;
+        const NetBlock& b = kBlocks[i];
         // biases padded with zeros to a multiple of 32 couts; conv1's is bias + 0.0f, conv2's the sum with the projection's
-        copy(kConv1B + i, v + kC1B, nullptr, 1);
-        copy(kSumB + i, v + kC2B, src[v + kResB], 1);
-        W.d[3 * i] = WinoPackDesc{src[v + kC1K], n->w[kWino1 + i], 9, b.cin, b.cout};
-        W.d[3 * i + 1] = WinoPackDesc{src[v + kC2K], n->w[kWino2 + i], 9, b.cout, b.cout};
-        W.d[3 * i + 2] = WinoPackDesc{src[v + kResK], n->w[kWinoR + i], 1, b.cin, b.cout};
+        copy(kConv1B + i, var(i, kC1B), nullptr, 1);
+        copy(kSumB + i, var(i, kC2B), src[var(i, kResB)], 1);
+        W.d[3 * i] = WinoPackDesc{src[var(i, kC1K)], n->w[kWino1 + i], 9, b.cin, b.cout};
+        W.d[3 * i + 1] = WinoPackDesc{src[var(i, kC2K)], n->w[kWino2 + i], 9, b.cout, b.cout};
+        W.d[3 * i + 2] = WinoPackDesc{src[var(i, kResK)], n->w[kWinoR + i], 1, b.cin, b.cout};
     }
     for (int j = 0; j < 10; ++j) copy(kHeadW + j, kVarHeads + j, nullptr, 0);
     hipLaunchKernelGGL(af_update_wino, dim3(kWinoPackBlocks, kWinoBufs), dim3(256), 0, st, W);
@@ -873,8 +848,23 @@ int32_t af_net_debug_scales(af_net* n, float* host_out, int32_t cap) {
 
 }  // extern "C"
 
-static int g_f16s_abl = 0;
-static int g_wino = 5;   // 5: fp16 split-operand implicit GEMM on 11x11 / 15x15 boards (default; other sizes run 1); 1: af_conv_wino (fp32 MFMA, Winograd)
+// The process-global knobs, by af_net_tune key
+static struct {
+    int conv = 5;        // 0: 5 = fp16 split-operand implicit GEMM on 11x11 / 15x15 boards (default; other sizes run 1); 1 = af_conv_wino (fp32 MFMA, Winograd)
+    int branch = 1;      // 4: value branch on a side stream (fp32 path: 1/0; 2 forces it on path 5)
+    int phead = 1;       // 5: 1 = af_policy_head_mfma for boards up to 11x11; 0 = VALU head
+    int f16s_bits = 0;   // 7: A/B and profiling bits of af_conv_f16s.hip (F16sBits)
+    int fhead = 1;       // 9: 1 = the split-operand path computes the heads itself (fused 1x1 conv + MFMA dense layers); 0 = af_value_head / af_policy_head_mfma
+} g_tune;
+
+extern "C" int af_net_tune(int32_t key, int32_t value) {
+    if (key == 0) { if (value != 1 && value != 5) return AF_NET_ERR_ARG; g_tune.conv = value; return AF_NET_OK; }
+    if (key == 4) { g_tune.branch = value; return AF_NET_OK; }
+    if (key == 5) { g_tune.phead = value; return AF_NET_OK; }
+    if (key == 7) { g_tune.f16s_bits = value; return AF_NET_OK; }
+    if (key == 9) { g_tune.fhead = value ? 1 : 0; return AF_NET_OK; }
+    return AF_NET_ERR_ARG;
+}
 
 static void launch_wino(hipStream_t st, const af_net* n, int batch, const float* in, const float* u, int cin,
                         const float* in2, const float* u2, int cin2, const float* bias, float* out, int cout) {
@@ -886,87 +876,82 @@ static void launch_wino(hipStream_t st, const af_net* n, int batch, const float*
     const int ngrp8 = (((ntb + 3) / 4) + 7) / 8 * 8;      // tile-block groups, padded to the 8-XCD interleave
     hipLaunchKernelGGL(af_conv_wino, dim3(ngrp8 * (cout / 32)), dim3(256), 0, st, a);
 }
+// block i of the fp32 path, in -> act[kO + 2 * i]: conv1 3x3 + ELU (network.py:54); conv2 3x3 (+) 1x1 projection, add, ELU (network.py:53,55,56)
+static void launch_wino_block(hipStream_t st, const af_net* n, int batch, int i, const float* in) {
+    const NetBlock& b = kBlocks[i];
+    float *g = n->act[kG + 2 * i], *o = n->act[kO + 2 * i];
+    launch_wino(st, n, batch, in, n->w[kWino1 + i], b.cin, nullptr, nullptr, 0, n->w[kConv1B + i], g, b.cout);
+    launch_wino(st, n, batch, g, n->w[kWino2 + i], b.cout, in, n->w[kWinoR + i], b.cin, n->w[kSumB + i], o, b.cout);
+}
 
+// the fp32 heads, on the fp32 planes [batch][32][PP] a branch ends in
+static void launch_value_head(hipStream_t st, const af_net* n, int batch, const float* o3, float* value) {
+    hipLaunchKernelGGL(af_value_head, dim3((batch + VPB - 1) / VPB), dim3(256), 0, st, o3, n->w[kVcW], n->w[kVcB], n->w[kV1W], n->w[kV1B],
+                       n->w[kV2W], n->w[kV2B], value, batch, n->S, n->WP, n->PP);
+}
+// boards up to 11x11: af_policy_head_mfma (16 positions per workgroup) or, with af_net_tune(5, 0), the VALU head at 8; larger boards: the VALU head at 4
+static void launch_policy_head(hipStream_t st, const af_net* n, int batch, const float* o5, float* policy) {
+    const int HW = n->HW, K = 16 * HW, KS = K + ((2 - K % 32) + 32) % 32;
+    const bool mfma = HW <= 128 && g_tune.phead;
+    const int ppb = mfma ? 16 : HW <= 128 ? 8 : 4;
+    const size_t lds = mfma ? (size_t)16 * KS * 4 : ((size_t)16 * HW * ppb + 512 + 4 * ppb) * 4;
+    const auto head = mfma ? af_policy_head_mfma : HW <= 128 ? af_policy_head<8> : af_policy_head<4>;
+    hipLaunchKernelGGL(head, dim3((batch + ppb - 1) / ppb), dim3(256), lds, st, o5, n->w[kPcW], n->w[kPcB], n->w[kPfW], n->w[kPfB], policy,
+                       batch, n->S, n->WP, n->PP);
+}
 
-static int g_phead = 1;          // 1: af_policy_head_mfma for boards up to 11x11; 0: VALU head
-static int g_branch = 1;         // 1: value branch on a side stream
-static int g_fhead = 1;          // 1: split-operand path computes the heads itself (fused 1x1 conv + MFMA dense layers); 0: af_value_head / af_policy_head_mfma
-
-// forward pass of positions [b0, b0+batch) on stream st
-static int forward_range(af_net* n, hipStream_t st, const float* planes_all, int b0, int batch, float* policy_all, float* value_all) {
-    const int S = n->S, HW = n->HW, WP = n->WP, PP = n->PP;
-    const float* planes = planes_all + (size_t)b0 * 3 * HW;
-    float* policy = policy_all + (size_t)b0 * HW;
-    float* value = value_all + b0;
-    const size_t po = (size_t)b0 * PP;
-    float* f0 = n->act[kF0] + po * 32;
-    float* g[5];
-    float* o[5];
-    for (int i = 0; i < 5; ++i) { g[i] = n->act[kG + 2 * i] + po * kBlocks[i].cout; o[i] = n->act[kO + 2 * i] + po * kBlocks[i].cout; }
-    const bool split16 = g_wino == 5 && n->f16s != nullptr;     // (board sizes without the split-operand path run the fp32 Winograd path)
-    const bool fhead = split16 && g_fhead;                 // heads fused into the split-operand path
-    F16sPlan plan = {};
-    if (split16) {
-        plan = f16s_plan(n->f16s, batch, g_f16s_abl, fhead);
-        // 11x11 with fused heads: <= 8 positions as one launch of dataflow roles instead of nine dependent launches (r6); otherwise the
-        // trunk, then both branches paired on this stream (fork and join of a side stream cost more than the value branch's kernels)
-        if (plan.form != kF16sBranches) return f16s_forward(n->f16s, plan, st, planes, value, policy) ? AF_NET_ERR_HIP : AF_NET_OK;
-        if (f16s_trunk(n->f16s, plan, st, planes)) return AF_NET_ERR_HIP;
-    } else {
-        hipLaunchKernelGGL(af_stem_conv, dim3(batch), dim3(256), 0, st, planes, n->w[kStemW], n->w[kStemB], f0, S, WP, PP);
-    }
-    const float* block_in[5] = {f0, o[0], o[1], o[1], o[3]};
-    // the value branch (block3 + head) only depends on the trunk output o[1]: it runs on a side stream,
-    // concurrently with the policy branch (blocks 4,5 + head), filling the SIMDs the 32/64-wide layers leave idle
-    // (r5: on the split-operand path the side stream is used by neither board size any more — 11x11 runs the value branch as workgroup
-    //  classes of the policy branch's launches (kF16sPaired above); 15x15 serialised is 0.7 % faster than forked, 2.653 vs 2.672 ms:
-    //  fork and join cost more than the tail filling returns.  af_net_tune(4, 2) forces the side stream for A/B.)
-    hipStream_t vs = st;
-    if (g_branch && n->branch_stream && (!split16 || g_branch == 2)) {
-        vs = n->branch_stream;
-    }
-    for (int i = split16 ? 2 : 0; i < 5; ++i) {
-        const Block& b = kBlocks[i];
-        hipStream_t st_main = st;
-        if (i == 2 && vs != st_main) {
-            NET_HIP_OK(hipEventRecord(n->ev_trunk, st_main));
-            NET_HIP_OK(hipStreamWaitEvent(vs, n->ev_trunk, 0));
-        }
-        hipStream_t st = (i == 2) ? vs : st_main;
-        if (split16) {
-            if (i == 2 && f16s_value_branch(n->f16s, plan, st, o[2], WP, PP, value)) return AF_NET_ERR_HIP;
-            if (i == 4 && f16s_policy_branch(n->f16s, plan, st, o[4], WP, PP, policy)) return AF_NET_ERR_HIP;
-        } else {
-            // conv1 3x3 + ELU (network.py:54); conv2 3x3 (+) 1x1 projection, add, ELU (network.py:53,55,56)
-            launch_wino(st, n, batch, block_in[i], n->w[kWino1 + i], b.cin, nullptr, nullptr, 0, n->w[kConv1B + i], g[i], b.cout);
-            launch_wino(st, n, batch, g[i], n->w[kWino2 + i], b.cout, block_in[i], n->w[kWinoR + i], b.cin, n->w[kSumB + i], o[i], b.cout);
-        }
-        if (i == 2) {
-            if (!fhead)
-            hipLaunchKernelGGL(af_value_head, dim3((batch + VPB - 1) / VPB), dim3(256), 0, st, o[2], n->w[kVcW], n->w[kVcB], n->w[kV1W], n->w[kV1B],
-                               n->w[kV2W], n->w[kV2B], value, batch, S, WP, PP);
-            if (vs != st_main) NET_HIP_OK(hipEventRecord(n->ev_value, vs));
-        }
-    }
-    if (fhead) {
-        // (the policy head ran inside f16s_policy_branch)
-    } else if (HW <= 128 && g_phead) {
-        const int K = 16 * HW, KS = K + ((2 - K % 32) + 32) % 32;
-        const size_t lds = (size_t)16 * KS * 4;
-        hipLaunchKernelGGL(af_policy_head_mfma, dim3((batch + 15) / 16), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
-                           n->w[kPfB], policy, batch, S, WP, PP);
-    } else if (HW <= 128) {
-        const size_t lds = ((size_t)16 * HW * 8 + 512 + 32) * 4;
-        hipLaunchKernelGGL((af_policy_head<8>), dim3((batch + 7) / 8), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
-                           n->w[kPfB], policy, batch, S, WP, PP);
-    } else {
-        const size_t lds = ((size_t)16 * HW * 4 + 512 + 16) * 4;
-        hipLaunchKernelGGL((af_policy_head<4>), dim3((batch + 3) / 4), dim3(256), lds, st, o[4], n->w[kPcW], n->w[kPcB], n->w[kPfW],
-                           n->w[kPfB], policy, batch, S, WP, PP);
-    }
-    if (vs != st) NET_HIP_OK(hipStreamWaitEvent(st, n->ev_value, 0));
-    NET_HIP_OK(hipGetLastError());
+// The value branch (block3 + head) only depends on the trunk output o2: on the handle's side stream it runs concurrently with the
+// policy branch (blocks 4,5 + head), filling the SIMDs the 32/64-wide layers leave idle.  vs is the value branch's stream: with
+// vs == st there is no side stream and nothing to do.  The fork, behind the trunk:
+static int fork_value(af_net* n, hipStream_t st, hipStream_t vs) {
+    if (vs != st) { NET_HIP_OK(hipEventRecord(n->ev_trunk, st)); NET_HIP_OK(hipStreamWaitEvent(vs, n->ev_trunk, 0)); }
     return AF_NET_OK;
+}
+// ... and the join: the record behind the value branch's last launch; the wait behind the policy branch's, which ends the forward
+static int value_done(af_net* n, hipStream_t st, hipStream_t vs) { if (vs != st) NET_HIP_OK(hipEventRecord(n->ev_value, vs)); return AF_NET_OK; }
+static int join_value(af_net* n, hipStream_t st, hipStream_t vs) {
+    if (vs != st) NET_HIP_OK(hipStreamWaitEvent(st, n->ev_value, 0));
+    NET_HIP_OK(hipGetLastError());        // every launch of the forward
+    return AF_NET_OK;
+}
+
+// fp32 Winograd path: stem, five blocks, both fp32 heads
+static int forward_wino(af_net* n, hipStream_t st, const float* planes, int batch, float* policy, float* value) {
+    float *f0 = n->act[kF0], *o1 = n->act[kO], *o2 = n->act[kO + 2], *o3 = n->act[kO + 4], *o4 = n->act[kO + 6], *o5 = n->act[kO + 8];   // block1 .. block5's outputs
+    hipLaunchKernelGGL(af_stem_conv, dim3(batch), dim3(256), 0, st, planes, n->w[kStemW], n->w[kStemB], f0, n->S, n->WP, n->PP);
+    launch_wino_block(st, n, batch, 0, f0);
+    launch_wino_block(st, n, batch, 1, o1);
+    const hipStream_t vs = g_tune.branch ? n->branch_stream : st;
+    if (const int rc = fork_value(n, st, vs)) return rc;
+    launch_wino_block(vs, n, batch, 2, o2);
+    launch_value_head(vs, n, batch, o3, value);
+    if (const int rc = value_done(n, st, vs)) return rc;
+    launch_wino_block(st, n, batch, 3, o2);
+    launch_wino_block(st, n, batch, 4, o4);
+    launch_policy_head(st, n, batch, o5, policy);
+    return join_value(n, st, vs);
+}
+
+// fp16 split-operand path (af_conv_f16s.hip)
+static int forward_f16s(af_net* n, hipStream_t st, const float* planes, int batch, float* policy, float* value) {
+    const bool fhead = g_tune.fhead;        // heads fused into the path; otherwise the branches end in o3 / o5 for the fp32 head kernels
+    const F16sPlan plan = f16s_plan(n->f16s, batch, g_tune.f16s_bits, fhead);
+    // 11x11 with fused heads: <= 8 positions as one launch of dataflow roles instead of nine dependent launches (r6); otherwise the
+    // trunk, then both branches paired on this stream (fork and join of a side stream cost more than the value branch's kernels)
+    if (plan.form != kF16sBranches) return f16s_forward(n->f16s, plan, st, planes, value, policy) ? AF_NET_ERR_HIP : AF_NET_OK;
+    float *o3 = n->act[kO + 4], *o5 = n->act[kO + 8];
+    if (f16s_trunk(n->f16s, plan, st, planes)) return AF_NET_ERR_HIP;
+    // (r5: on this path the side stream is used by neither board size any more — 11x11 runs the value branch as workgroup classes of the
+    //  policy branch's launches (kF16sPaired above); 15x15 serialised is 0.7 % faster than forked, 2.653 vs 2.672 ms: fork and join cost
+    //  more than the tail filling returns.  af_net_tune(4, 2) forces the side stream for A/B.)
+    const hipStream_t vs = g_tune.branch == 2 ? n->branch_stream : st;
+    if (const int rc = fork_value(n, st, vs)) return rc;
+    if (f16s_value_branch(n->f16s, plan, vs, o3, n->WP, n->PP, value)) return AF_NET_ERR_HIP;
+    if (!fhead) launch_value_head(vs, n, batch, o3, value);
+    if (const int rc = value_done(n, st, vs)) return rc;
+    if (f16s_policy_branch(n->f16s, plan, st, o5, n->WP, n->PP, policy)) return AF_NET_ERR_HIP;
+    if (!fhead) launch_policy_head(st, n, batch, o5, policy);
+    return join_value(n, st, vs);
 }
 
 extern "C" {
@@ -976,16 +961,8 @@ int af_net_forward(af_net* n, void* stream, const float* planes, int32_t batch, 
     if (!n->ready) return AF_NET_ERR_STATE;
     // (r1-r5 A/B records, removed from the source in r6: concurrent sub-batches on side streams and sequential sub-batches that keep a
     //  layer's output inside the Infinity Cache — 1.415 / 1.621 ms per 4096 positions as 2 / 4 sub-batches against 1.330: profiles/r5_41)
-    return forward_range(n, (hipStream_t)stream, planes, 0, batch, policy, value);
-}
-
-int af_net_tune(int32_t key, int32_t value) {
-    if (key == 0) { if (value != 1 && value != 5) return AF_NET_ERR_ARG; g_wino = value; return AF_NET_OK; }   // 0: conv path (5 split fp16, 1 fp32 Winograd)
-    if (key == 5) { g_phead = value; return AF_NET_OK; }                            // 5: MFMA policy head of the fp32 path (1/0)
-    if (key == 4) { g_branch = value; return AF_NET_OK; }                           // 4: value branch on a side stream (fp32 path: 1/0; 2 forces it on path 5)
-    if (key == 9) { g_fhead = value ? 1 : 0; return AF_NET_OK; }                    // 9: heads on the split-operand path (1/0)
-    if (key == 7) { g_f16s_abl = value; return AF_NET_OK; }                         // 7: A/B and profiling bits of af_conv_f16s.hip (F16sBits)
-    return AF_NET_ERR_ARG;
+    if (g_tune.conv == 5 && n->f16s) return forward_f16s(n, (hipStream_t)stream, planes, batch, policy, value);
+    return forward_wino(n, (hipStream_t)stream, planes, batch, policy, value);      // (also: board sizes without the split-operand path)
 }
 
 int af_net_debug_activation(af_net* n, int32_t which, int32_t batch, float* host_out) {
@@ -1002,7 +979,7 @@ int af_net_small_forward_error(af_net* n) {
 int64_t af_net_flops_per_position(const af_net* n) {
     const int64_t HW = n->HW;
     int64_t mac = 75 * 32 * HW;
-    for (const Block& b : kBlocks) mac += ((int64_t)9 * b.cin * b.cout + (int64_t)9 * b.cout * b.cout + (int64_t)b.cin * b.cout) * HW;
+    for (const NetBlock& b : kBlocks) mac += ((int64_t)9 * b.cin * b.cout + (int64_t)9 * b.cout * b.cout + (int64_t)b.cin * b.cout) * HW;
     mac += 32 * 4 * HW + 4 * HW * 64 + 64 + 32 * 16 * HW + 16 * HW * HW;
     return 2 * mac;
 }

@@ -496,9 +496,9 @@ class SelfPlayEngine:
         return (int(n), self.engine.params_key(), ver() if ver is not None else None)
 
     def run_ticks_graph(self, n=16, timed=False, stamped=False):
-        """n ticks replayed as ONE HIP graph on the current stream (the tick kernel, the forward's 13 launches with the value
-        branch's fork / join, and at the end a 16-byte copy of the engine's progress words into pinned host memory).  Returns at
-        once; progress_lagged() reads the words one replay later, so polling never drains the device.  The graph is keyed on
+        """n ticks replayed as ONE HIP graph on the current stream (the tick kernel, the forward's launches — on 11x11 above 8 games
+        nine on this one stream, no side-stream fork / join — and at the end a 16-byte copy of the engine's progress words into
+        pinned host memory).  Returns at once; progress_lagged() reads the words one replay later, so polling never drains the device.  The graph is keyed on
         everything a launch has baked in: n, the engine's by-value parameters (training flag, simulation budget, per-launch select
         budget) and the evaluator's weight version — a change drops it, one eager tick re-packs the weights and the batch is
         captured again (same protocol as Player._search_batch).  A failing capture raises: there is no silent eager fallback.

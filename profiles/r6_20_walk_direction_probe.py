@@ -1,4 +1,5 @@
-"""Does the ORDER in which a layer walks the batch matter?  (r6)  Every activation tensor of the 11x11 forward at 4096 positions is
+"""Needs profiles/r6_20_walk_direction.patch applied: the key-7 bits 0x2000 / 0x4000 it drives exist only there.
+Does the ORDER in which a layer walks the batch matter?  (r6)  Every activation tensor of the 11x11 forward at 4096 positions is
 75-302 MB, the Infinity Cache 256 MB: a consumer that walks the batch in its producer's order starts on the data that left the
 cache first.  af_net_tune(7, 0x2000) reverses the walk of the even layers (boustrophedon: a launch starts on what its producer
 wrote last); 0x6000 reverses every layer (control: today's order, mirrored).  Same bits per position in every variant — checked.
@@ -9,7 +10,7 @@ import sys
 
 import torch
 
-R_ = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R_ = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # the repository root
 sys.path.insert(0, R_)
 from alphafive_amd import net_hip                                     # noqa: E402
 from alphafive_amd.network import ResNet                               # noqa: E402

@@ -270,3 +270,47 @@ def test_forward_variants_match_the_recorded_digests(S, B):
     assert got == recorded
     for s in m.SAME_BITS_AS_DEFAULT:
         assert got[m.setting_key(s)] == got["default"], (m.shape_key(S, B), m.setting_key(s))
+
+
+@pytest.mark.parametrize("S,B", [(7, 5), (11, 17)])
+def test_fp32_path_without_side_stream_and_with_valu_policy_head(S, B):
+    """The two settings of the fp32 Winograd path (af_net_tune(0, 1)) that no recorded digest takes: the value branch on the caller's
+    stream (af_net_tune(4, 0): the same kernels in one queue, so the bits of the side-stream default) and the VALU policy head
+    (af_net_tune(5, 0): another summation order for the policy, held to the fp64 restatement; the value does not pass through it).
+    7x7, 5 positions: a board size without a split-operand handle, one head workgroup; 11x11, 17 positions: two workgroups of the
+    MFMA head with a ragged tail, three of the VALU head."""
+    import hashlib
+    import torch
+    from alphafive_amd import net_hip
+    from alphafive_amd.network import ResNet
+    net = ResNet(S, device="cuda", seed=S)
+    if S == 11:
+        net.load_npz(W)
+    pv = net.select_backend("hip")
+    x = _positions(S, B, seed=B)
+    xt = torch.from_numpy(x).cuda()
+    p64, v64 = net_fp64.forward(net.variables, x)
+
+    def run(key, value):
+        net_hip.tune(key, value)
+        p, v = (t.cpu().numpy().copy() for t in pv(xt))
+        net_hip.tune(key, 1)
+        print("S%d_B%d tune(%d, %d): policy %s value %s  |dp| %.3g |dv| %.3g" % (
+            S, B, key, value, hashlib.sha256(p.tobytes()).hexdigest()[:16], hashlib.sha256(v.tobytes()).hexdigest()[:16],
+            np.abs(p - p64).max(), np.abs(v - v64).max()))
+        return p, v
+
+    try:
+        net_hip.tune(0, 1)
+        p_side, v_side = run(4, 1)
+        p_one, v_one = run(4, 0)
+        p_mfma, v_mfma = run(5, 1)
+        p_valu, v_valu = run(5, 0)
+    finally:
+        net_hip.tune(0, 5)
+        net_hip.tune(4, 1)
+        net_hip.tune(5, 1)
+    assert p_side.shape == (B, S * S) and v_side.shape == (B,)
+    assert (p_one.view(np.uint32) == p_side.view(np.uint32)).all() and (v_one.view(np.uint32) == v_side.view(np.uint32)).all()
+    assert (v_valu.view(np.uint32) == v_mfma.view(np.uint32)).all()
+    assert np.abs(p_valu - p64).max() < 1e-5
