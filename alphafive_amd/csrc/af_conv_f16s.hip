@@ -8,6 +8,16 @@
 // layer so that their halves sit in the fp16 normal range; the epilogue multiplies back (exact).  Measured against
 // the fp64 restatement of the network: |dv| 1.1e-6, |dp| 1.0e-6 (fp32 arithmetic: 4e-7), bar 1e-5.
 //
+// Range (tests/test_gpu_f16s_exact.py holds the kernels to it, tests/test_f16s_reference_cpu.py watches the shipped checkpoint's
+// headroom).  Only the WEIGHTS carry a scale; activations are stored unscaled, hi = fp16(f), lo = fp16(f - hi):
+//   |f| < 65504   the stated range of every stored activation (stem, conv1 / conv2 outputs, head convolution outputs).  The split has
+//                 relative error 2^-22 while lo is an fp16 normal (|f| >= ~2^-3) and absolute error 2^-25 below that (lo, then hi, are
+//                 fp16 subnormals, which the MFMA keeps): small activations lose relative, not absolute, accuracy.
+//   |f| >= 65520  hi = +-inf and lo = NaN or -+inf.  UNDEFINED from here on — and not necessarily visible: the next layer's accumulator
+//                 becomes NaN, and elu1 / elu2 below turn NaN into -1.0 (fmaxf(NaN, 0) = 0, 0 - 1 = -1, fmaxf(NaN, -1) = -1), so the
+//                 network's outputs can be finite, plausible and wrong.  A finiteness check of policy and value proves nothing
+//                 about range; the per-stage maxima of the fp64 restatement do (shipped checkpoint: 376 at most, 174x below).
+//
 // Activations live in HBM already split, in "S32" layout: [position][C/32 slabs][hi|lo][4 unit rows][144 units][8 ch]
 // fp16 — a unit is 8 channels of one pixel (16 bytes = one lane's MFMA B operand), pixel n = 11y + x sits at unit n + 11
 // (rows back to back, 11 zero units above, 12 below; the zeros are never written).  A 32-channel slab is 18,432
@@ -2435,10 +2445,27 @@ int f16s_small_forward_error(f16s_net* n) {
     return e;
 }
 
-// debug / tests: activation `which` (0 f0, 1 g1, 2 o1, 3 g2, 4 o2, 5 g3, 6 g4, 7 o4, 8 g5) of the first `batch` positions as
-// fp32 [batch][C][S*S] on the host (hi + lo).  Returns the channel count or < 0.
+// debug / tests: activation `which` (0 f0, 1 g1, 2 o1, 3 g2, 4 o2, 5 g3, 6 g4, 7 o4, 8 g5, 9 / 10 the value / policy head's 1x1
+// convolution output hx[0] / hx[1]) of the first `batch` positions as fp32 [batch][C][S*S] on the host (hi + lo), on both geometries.
+// Returns the channel count or < 0.  Which of these buffers a forward writes depends on its plan (include/af_net.h has the table):
+// g3 and g5 only without fused blocks, hx only with the fused heads; o3 and o5 never leave the registers.
 int f16s_read_activation(f16s_net* n, int which, int batch, float* host) {
     if (!n || batch < 1 || batch > n->max_batch) return -1;
+    if (which == 9 || which == 10) {
+        // value: [position][hi|lo][HXP pixel slots][4] fp16, policy: ... [16]; pixel n of the board sits in slot n on both geometries
+        const int C = which == 9 ? 4 : 16, hxp = 128 * (n->S == 11 ? 1 : 2), npix = n->S * n->S;
+        const size_t pos_h = (size_t)2 * hxp * C, lo_h = (size_t)hxp * C;                                    // in fp16 elements
+        std::vector<_Float16> h((size_t)batch * pos_h);
+        FS_HIP_OK(hipDeviceSynchronize());
+        FS_HIP_OK(hipMemcpy(h.data(), n->hx[which - 9], h.size() * 2, hipMemcpyDeviceToHost));
+        for (int b = 0; b < batch; ++b)
+            for (int c = 0; c < C; ++c)
+                for (int p = 0; p < npix; ++p) {
+                    const size_t idx = (size_t)b * pos_h + (size_t)p * C + c;
+                    host[((size_t)b * C + c) * npix + p] = (float)h[idx] + (float)h[idx + lo_h];
+                }
+        return C;
+    }
     const char* bufs[9] = {n->f0, n->g[0], n->o[0], n->g[1], n->o[1], n->g[2], n->g[3], n->o[3], n->g[4]};
     const int chans[9] = {32, 64, 64, 128, 128, 32, 64, 64, 32};
     if (which < 0 || which > 8) return -1;

@@ -39,6 +39,7 @@ def lib():
         L.af_net_debug_scales.restype = C.c_int32
         L.af_net_flops_per_position.argtypes = [vp]
         L.af_net_flops_per_position.restype = C.c_int64
+        L.af_net_debug_activation.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
         L.af_net_small_forward_error.argtypes = [vp]
         L.af_net_strerror.argtypes = [C.c_int]
         L.af_net_strerror.restype = C.c_char_p
@@ -114,6 +115,22 @@ class HipNet(object):
         n = lib().af_net_debug_scales(self._h, buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size)
         _check(n, "af_net_debug_scales")
         return buf[:n].copy()
+
+    # af_net_debug_activation's `which` -> channel count; the names are the keys of oracle.net_fp64.intermediates
+    ACTIVATIONS = {"f0": (0, 32), "g1": (1, 64), "o1": (2, 64), "g2": (3, 128), "o2": (4, 128), "g3": (5, 32), "g4": (6, 64),
+                   "o4": (7, 64), "g5": (8, 32), "vconv": (9, 4), "pconv": (10, 16)}
+
+    def debug_activation(self, which, batch):
+        """Tests: intermediate activation `which` (an index, or a name of ACTIVATIONS) of the first `batch` positions of the last
+        forward of the split-operand path as float32 [batch][C][S*S] (af_net_debug_activation; synchronises).  include/af_net.h
+        lists which launch forms write which buffer — a buffer the last forward skipped holds an earlier forward's values."""
+        idx, chans = self.ACTIVATIONS[which] if isinstance(which, str) else next(v for v in self.ACTIVATIONS.values() if v[0] == which)
+        out = np.empty((batch, chans, self.S * self.S), np.float32)
+        c = lib().af_net_debug_activation(self._h, idx, batch, out.ctypes.data_as(C.POINTER(C.c_float)))
+        _check(c, "af_net_debug_activation")
+        if c != chans:
+            raise NetError(f"af_net_debug_activation({idx}) returned {c} channels, expected {chans}")
+        return out
 
     def weights_version(self):
         """Count of load() and load_device() calls: what a captured graph over this handle (SelfPlayEngine.run_ticks_graph) is keyed on."""

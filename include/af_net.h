@@ -88,9 +88,25 @@ int af_net_forward(af_net* n, void* stream, const float* planes_dev, int32_t bat
  * (removed in r6 with the kernels they selected: conv paths 0 / 2 / 3 / 4, keys 1 / 2 / 3 / 6 / 8) */
 int af_net_tune(int32_t key, int32_t value);
 
-/* Tests / debugging of the fp16 split-operand path (conv path 5, 11x11 boards): intermediate activation `which`
- * (0 stem, 1/2 block1 conv1/output, 3/4 block2, 5 block3 conv1, 6/7 block4, 8 block5 conv1) of the first `batch`
- * positions of the last forward, as fp32 [batch][C][121] on the host.  Returns the channel count C or <0. */
+/* Tests / debugging of the fp16 split-operand path (conv path 5, 11x11 and 15x15 boards): intermediate activation `which`
+ * (0 stem f0, 1/2 block1 conv1 g1 / output o1, 3/4 block2 g2 / o2, 5 block3 conv1 g3, 6/7 block4 g4 / o4, 8 block5 conv1 g5,
+ * 9 / 10 the value / policy head's 1x1 convolution output after its ELU: 4 / 16 channels, the dense layers' input) of the first
+ * `batch` positions of the last forward, as fp32 [batch][C][S*S] on the host (hi + lo of the stored halves).  Returns the channel
+ * count C or <0.  Synchronises the device.  The call copies a buffer; whether the last forward WROTE it depends on its launch form:
+ *
+ *   which                      written by
+ *   0 1 2 3 4 6 7              every form on both board sizes (roles, paired, branches; tile split or whole positions)
+ *   5 (g3), 8 (g5)             15x15 always; 11x11 only with af_net_tune(7, 256) or af_net_tune(9, 0) — with fused blocks (the
+ *                              11x11 default) the 32-channel intermediate stays in LDS and the buffer keeps what an earlier forward left
+ *   9, 10                      key 9 = 1 (default: fused heads); with key 9 = 0 the branches end in fp32 planes instead
+ *   o3, o5 (block 3 / 5 out)   never stored: they feed the head convolution from registers
+ *
+ * Range of the split-operand path: every stored activation f (all of the above) must satisfy |f| < 65504, the fp16 maximum —
+ * activations are stored unscaled as fp16 hi + lo, only weights carry a power-of-two scale.  Within the range the split is good to
+ * 2^-22 relative, and to 2^-25 absolute below |f| ~ 2^-3 (fp16 subnormal halves are kept).  Beyond it the outputs are UNDEFINED and
+ * may well be finite: the overflowed halves are inf / NaN, the next layer's sum is NaN, and the kernels' ELU (a max / min form)
+ * maps NaN to -1.0.  Finite policy and value therefore do not show that a weight set is in range; the per-layer maxima of
+ * oracle/net_fp64.intermediates do (shipped checkpoint: at most 376). */
 int af_net_debug_activation(af_net* n, int32_t which, int32_t batch, float* host_out);
 
 /* Tests: weight-derived device buffer `index` copied to host_out (cap_bytes must hold it); returns its size in bytes (also when
