@@ -1,9 +1,16 @@
 // af_tower_bf16.hip — bf16 residual tower for gfx950 (C ABI: include/af_tower_bf16.h).
 //
-// One kernel, af_tower_conv<PROJ>, is a 3x3 convolution 128 -> 128 over 11x11 boards as an implicit GEMM
+// Two kernels, af_tower_conv<PROJ, DEPTH> and af_tower_conv3<PROJ, DEPTH>, compute the same 3x3 convolution 128 -> 128 over
+// 11x11 boards as an implicit GEMM
 //   out[cout][pixel] = sum_{tap, cin} W[cout][cin][tap] * in[cin][pixel + tap offset]
 // on v_mfma_f32_32x32x16_bf16 (M = 32 couts, N = 32 pixels, K = 16 cin of one tap), plus, for the second
 // convolution of a block (PROJ), 8 more k-steps that fold the block's 1x1 projection of the block input in.
+// They share everything described below — set-up, staging, LDS layout, tap addresses: the functions in front of them — and
+// differ in their position loops only: af_tower_conv runs a position's MFMAs over four accumulator sets and then its epilogue;
+// af_tower_conv3 runs two phases of two pixel tiles and issues the finished pair's epilogue inside the other pair's MFMA stream
+// (see its own comment).  Which one runs where is tune key 3 (kConv / pick in the host part): by default af_tower_conv3 for a
+// block's first convolution and af_tower_conv for its second (PROJ); 0 = af_tower_conv for both, at the ring depth of key 0;
+// 2 = af_tower_conv3 for both.
 //
 // Work split (weight-stationary, persistent): a workgroup = 4 waves = the 4 cout tiles of 32; each wave keeps
 // ALL its weights — 32 couts x (9*128 [+128]) k = 72 [80] A fragments of 8 bf16 = 288 [320] registers — resident
@@ -39,20 +46,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
         if (err_ != hipSuccess) return AF_TOWER_ERR_HIP;     \
     } while (0)
 
-// Build-time variants (same experiments as af_conv_f16s.hip, r3; profiles/r3_18_tower_ab.txt): nt hint on the LDS-DMA loads: 5.29 -> 5.17 ms per
-// 8192-position tower pass; lanes past the board read zeros: within noise (5.16-5.17 with both)
-#ifndef AF_TOWER_NT_LOAD
-#define AF_TOWER_NT_LOAD 1
-#endif
-#ifndef AF_TOWER_ZPAD
-#define AF_TOWER_ZPAD 1
-#endif
-#ifndef AF_TOWER_VSLACK
-#define AF_TOWER_VSLACK 88       // architectural VGPRs left to everything that is not a weight fragment or the B-fragment ring
-#endif
-#ifndef AF_TOWER_EPI_SCALAR
-#define AF_TOWER_EPI_SCALAR 1    // af_tower_conv3: epilogue stages of two single-issue VALU instructions per MFMA gap (r5); 0 = r4's 2-vector stages
-#endif
+// (r3 A/B record, profiles/r3_18_tower_ab.txt; both were build-time switches until nothing built them any other way: the nt hint on
+//  the LDS-DMA loads: 5.29 -> 5.17 ms per 8192-position tower pass; lanes past the board read zeros: within noise, 5.16-5.17 with both)
+constexpr int kVSlack = 88;      // architectural VGPRs left to everything that is not a weight fragment or the B-fragment ring
 #ifndef AF_TOWER_ABL_NOLDS
 #define AF_TOWER_ABL_NOLDS 0     // profiling build: af_tower_conv without its B-fragment reads (results wrong by design)
 #endif
@@ -60,13 +56,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // LDS-DMA: 16 bytes per lane from global memory into LDS at (wave-uniform lds_dst) + lane*16; counted on vmcnt.
 __device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
     unsigned keep;
-#if AF_TOWER_NT_LOAD
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#else
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#endif
 }
 
 // ELU as max(x, min(exp(x), 1) - 1): x > 0 ? x : exp(x) - 1 with one v_max_f32 instead of compare + select and the clamp riding on
@@ -91,11 +82,8 @@ __device__ __forceinline__ f32x2 elu2(f32x2 x) {
 // First position of a persistent workgroup (r4, as in af_conv_f16s.hip): consecutive workgroup ids sit on consecutive XCDs, so with
 // pos = blockIdx.x the 32 workgroups of XCD k would walk the positions = k (mod 8) only; XCD k takes the contiguous positions
 // 32k..32k+31 (+ gridDim.x per pass) instead.  A position's result does not depend on the workgroup that computes it.
-#ifndef AF_TOWER_XCD_SWIZZLE
-#define AF_TOWER_XCD_SWIZZLE 1
-#endif
 __device__ __forceinline__ int first_position() {
-    if (AF_TOWER_XCD_SWIZZLE && (gridDim.x & 7) == 0) return (int)(blockIdx.x >> 3) + (int)(gridDim.x >> 3) * (int)(blockIdx.x & 7);
+    if ((gridDim.x & 7) == 0) return (int)(blockIdx.x >> 3) + (int)(gridDim.x >> 3) * (int)(blockIdx.x & 7);
     return (int)blockIdx.x;
 }
 
@@ -123,50 +111,53 @@ __device__ unsigned long long g_tower_cyc[2][256][4][5];
 #else
 #define TT(v)
 #endif
-// One convolution layer over this workgroup's positions.
-template <bool PROJ, int DEPTH>
-__device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
-    constexpr int NS = PROJ ? 80 : 72;
-    const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
 
-    auto stage_round = [&](const char* src, int pos, uint32_t off, int r) {   // 4 KB piece r of a position's plane -> LDS
-        const char* gp = src + (size_t)pos * kPlaneB + threadIdx.x * 16u + r * 4096;
-        const uint32_t ld = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + off + wv * 1024u + r * 4096u));
-        glds16(gp, ld);
-    };
-    auto stage = [&](const char* src, int pos, uint32_t off) {          // one position's plane -> LDS at byte offset off
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) stage_round(src, pos, off, r);
-    };
-    int pos = first_position();
-    if (pos >= A.batch) return;
-    constexpr uint32_t kZoff = kLds0 + (PROJ ? 3u : 2u) * kPlaneB;      // the zero region follows the planes
-    for (uint32_t u = threadIdx.x; u < kZeroB / 16; u += 256) *reinterpret_cast<uint4*>(smem + kZoff + u * 16) = uint4{0, 0, 0, 0};
-    stage(A.in, pos, 0u);
-    if (PROJ) stage(A.in2, pos, 2u * kPlaneB);
+// ---- what both convolution kernels are made of.  Free functions over the kernels' own register arrays, taken BY REFERENCE: gathered
+// into a struct that a member function fills, the same code made hipcc park values in accumulator registers and read them back inside
+// af_tower_conv3's steady-state MFMA blocks (+2 to +8 v_accvgpr_read_b32 per 16-MFMA block: profiles/tower_conv_shared_setup.md).
+// lane, kg = lane >> 5 and nn = lane & 31 are the kernel's, computed at its top (derived again in here they cost registers) ----
 
-    // resident weights and bias
-    bf16x8 W[NS];
-    {
-        const uint4* wp = A.w + ((size_t)wv * NS * 64 + lane);
+constexpr uint32_t zero_off(bool proj) { return kLds0 + (proj ? 3u : 2u) * kPlaneB; }   // LDS: [256 B][g0][g1]([h])[zero region]
+constexpr uint32_t lds_bytes(bool proj) { return zero_off(proj) + kZeroB; }             // a launch's dynamic LDS
+
+// 4 KB piece r of a position's plane -> LDS at byte offset off behind lds0 (wave wv's 1 KB of it)
+__device__ __forceinline__ void stage_round(uint32_t lds0, uint32_t wv, const char* src, int pos, uint32_t off, int r) {
+    const char* gp = src + (size_t)pos * kPlaneB + threadIdx.x * 16u + r * 4096;
+    const uint32_t ld = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + off + wv * 1024u + r * 4096u));
+    glds16(gp, ld);
+}
+
+// the zero region, and the planes of the workgroup's first position on their way
+template <bool PROJ>
+__device__ __forceinline__ void stage_first(const TowerArgs& A, char* smem, uint32_t lds0, uint32_t wv, int pos) {
+    for (uint32_t u = threadIdx.x; u < kZeroB / 16; u += 256) *reinterpret_cast<uint4*>(smem + zero_off(PROJ) + u * 16) = uint4{0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint4 v = wp[s * 64];
-            __builtin_memcpy(&W[s], &v, 16);
-        }
+    for (int r = 0; r < kRounds; ++r) stage_round(lds0, wv, A.in, pos, 0u, r);
+    if (PROJ) {
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) stage_round(lds0, wv, A.in2, pos, 2u * kPlaneB, r);
     }
-    float bias_r[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bias_r[r] = A.bias[32 * wv + 16 * kg + r];   // MFMA rows are permuted at pack time: see pack_tower
+}
 
-    // the lane's pixel in each of the 4 pixel tiles: LDS byte base of tap (0,0) (one row up, one pixel left).  Rows are
-    // stored back to back (no pad columns: consecutive lanes read consecutive 16-byte units, which is what keeps
-    // ds_read_b128 conflict-free); for the left / right taps of the first / last pixel of a row the lane reads zeros
-    // from a dedicated LDS region (a different base register, no per-read VALU).
-    uint32_t lb[4], ob[4], zb[4];
-    bool ok[4], edgeL[4], edgeR[4];
+// resident weights and bias
+template <int NS>
+__device__ __forceinline__ void load_weights(const TowerArgs& A, uint32_t wv, int lane, int kg, bf16x8 (&W)[NS], float (&bias_r)[16]) {
+    const uint4* wp = A.w + ((size_t)wv * NS * 64 + lane);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const uint4 v = wp[s * 64];
+        __builtin_memcpy(&W[s], &v, 16);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bias_r[r] = A.bias[32 * wv + 16 * kg + r];   // MFMA rows are permuted at pack time: see pack_perm
+}
+
+// the lane's pixel in each of the 4 pixel tiles: LDS byte base of tap (0,0) (one row up, one pixel left).  Rows are
+// stored back to back (no pad columns: consecutive lanes read consecutive 16-byte units, which is what keeps
+// ds_read_b128 conflict-free); for the left / right taps of the first / last pixel of a row the lane reads zeros
+// from a dedicated LDS region (a different base register, no per-read VALU).
+__device__ __forceinline__ void pixel_bases(uint32_t zoff, int kg, int nn, uint32_t (&lb)[4], uint32_t (&ob)[4], uint32_t (&zb)[4],
+                                            bool (&ok)[4], bool (&edgeL)[4], bool (&edgeR)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int n = 32 * j + nn;
@@ -176,12 +167,16 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
         edgeL[j] = x == 0; edgeR[j] = x == kS - 1;
         lb[j] = kLds0 + (uint32_t)(kg * kPIX + nc + kS - (kS + 1)) * 16u;
         ob[j] = (uint32_t)(nc + kS) * 16u;                              // output unit of the pixel
-        zb[j] = kZoff + (lb[j] & 255u);                                 // same banks as the lane's own unit: stays conflict-free
+        zb[j] = zoff + (lb[j] & 255u);                                  // same banks as the lane's own unit: stays conflict-free
     }
-    // Pin the weight / bias loads' completion HERE: hipcc otherwise sinks its counted vmcnt waits to the first use of
-    // each fragment inside the position loop, where they would also wait for the (to hipcc invisible) LDS-DMA of the
-    // next position that is issued at the top of every iteration.
-    constexpr int kNVfit = (256 - 4 * DEPTH - AF_TOWER_VSLACK) / 4, kNVmin = NS - (256 - 64) / 4;   // fragments kept in VGPRs
+}
+
+// Pin the weight / bias loads' completion HERE, in front of the position loop: hipcc otherwise sinks its counted vmcnt waits to
+// the first use of each fragment inside the loop, where they would also wait for the (to hipcc invisible) LDS-DMA of the
+// next position that is issued at the top of every iteration.  Then wait for the first planes and meet the other waves.
+template <int NS, int DEPTH>
+__device__ __forceinline__ void pin_and_sync(bf16x8 (&W)[NS], float (&bias_r)[16]) {
+    constexpr int kNVfit = (256 - 4 * DEPTH - kVSlack) / 4, kNVmin = NS - (256 - 64) / 4;   // fragments kept in VGPRs
     constexpr int NV = kNVfit > kNVmin ? kNVfit : kNVmin;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -195,6 +190,49 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
     for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bias_r[r]));
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // first planes landed, zero region written
     __builtin_amdgcn_s_barrier();
+}
+
+// a position's read bases for the centre / left / right tap columns: its plane (LDS buffer gcur), or the zero region for lanes
+// past the board and for the neighbour a row does not have
+__device__ __forceinline__ void tap_bases(uint32_t gcur, const uint32_t (&lb)[4], const uint32_t (&zb)[4], const bool (&ok)[4],
+                                          const bool (&edgeL)[4], const bool (&edgeR)[4], uint32_t (&bC)[4], uint32_t (&bL)[4], uint32_t (&bR)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bC[j] = !ok[j] ? zb[j] : gcur + lb[j];
+        bL[j] = edgeL[j] ? zb[j] : bC[j];
+        bR[j] = edgeR[j] ? zb[j] : bC[j];
+    }
+}
+
+// B fragment of projection k-step cc (block-input plane, the pixel itself) ...
+__device__ __forceinline__ bf16x8 proj_tap(const char* smem, uint32_t lbj, int cc) {
+    return *reinterpret_cast<const bf16x8*>(smem + 2u * kPlaneB + lbj + (uint32_t)(2 * cc * kPIX + kS + 1) * 16u);
+}
+// ... and of tap t (0..8, row-major), cin step cc of the 3x3 convolution, from the base of the tap's column: bL / bC / bR for
+// t % 3 = 0 / 1 / 2.  The caller picks the column with a conditional of its own: with that choice in here — as a select, through
+// a helper or as a table indexed by t % 3 — hipcc allocates af_tower_conv<true, *> differently (504 -> 496 VGPRs at depth 8, other
+// spills at 12 and 16), and this file's kernels are held to the code they had (profiles/tower_conv_shared_setup.md).
+__device__ __forceinline__ bf16x8 conv_tap(const char* smem, uint32_t base, int t, int cc) {
+    return *reinterpret_cast<const bf16x8*>(smem + base + (uint32_t)(2 * cc * kPIX + (t / 3) * kS + (t % 3)) * 16u);
+}
+
+// One convolution layer over this workgroup's positions.
+template <bool PROJ, int DEPTH>
+__device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
+    constexpr int NS = PROJ ? 80 : 72;
+    const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
+    int pos = first_position();
+    if (pos >= A.batch) return;
+    stage_first<PROJ>(A, smem, lds0, wv, pos);
+    bf16x8 W[NS];
+    float bias_r[16];
+    load_weights(A, wv, lane, kg, W, bias_r);
+    uint32_t lb[4], ob[4], zb[4];
+    bool ok[4], edgeL[4], edgeR[4];
+    pixel_bases(zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
+    pin_and_sync<NS, DEPTH>(W, bias_r);
 
 #ifdef AF_TOWER_TIMING
     unsigned long long tacc[5] = {0, 0, 0, 0, 0};
@@ -203,13 +241,8 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
         const uint32_t gcur = (it & 1) ? kPlaneB : 0u, gnxt = kPlaneB - gcur;
         const int nxt = pos + (int)gridDim.x;
         const bool more = nxt < A.batch && !(A.abl & 1);
-        uint32_t bC[4], bL[4], bR[4];                                   // read bases for the centre / left / right tap columns
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            bC[j] = (AF_TOWER_ZPAD && !ok[j]) ? zb[j] : gcur + lb[j];
-            bL[j] = edgeL[j] ? zb[j] : bC[j];
-            bR[j] = edgeR[j] ? zb[j] : bC[j];
-        }
+        uint32_t bC[4], bL[4], bR[4];
+        tap_bases(gcur, lb, zb, ok, edgeL, edgeR, bC, bL, bR);
         TT(t0);
         f32x16 acc[4];
 #pragma unroll
@@ -222,13 +255,9 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
         constexpr int NM = NS * 4, NPJ = PROJ ? 32 : 0;
         auto rd = [&](int i) -> bf16x8 {
             const int j = i & 3;
-            if (i < NPJ) {
-                const int cc = i >> 2;
-                return *reinterpret_cast<const bf16x8*>(smem + 2u * kPlaneB + lb[j] + (uint32_t)(2 * cc * kPIX + kS + 1) * 16u);
-            }
-            const int s_ = (i - NPJ) >> 2, t = s_ >> 3, cc = s_ & 7;
-            const uint32_t base = t % 3 == 0 ? bL[j] : (t % 3 == 2 ? bR[j] : bC[j]);
-            return *reinterpret_cast<const bf16x8*>(smem + base + (uint32_t)(2 * cc * kPIX + (t / 3) * kS + (t % 3)) * 16u);
+            if (i < NPJ) return proj_tap(smem, lb[j], i >> 2);
+            const int s_ = (i - NPJ) >> 2, t = s_ >> 3;
+            return conv_tap(smem, t % 3 == 0 ? bL[j] : (t % 3 == 2 ? bR[j] : bC[j]), t, s_ & 7);
         };
         bf16x8 ring[DEPTH];
 #pragma unroll
@@ -244,8 +273,8 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
             // the next position's planes are requested one 4 KB piece every 16 MFMAs (an LDS-DMA costs ~5 issue slots:
             // in one burst they would stall the matrix pipe for the whole burst)
-            if (i % 16 == 0 && i / 16 < kRounds && more) stage_round(A.in, nxt, gnxt, i / 16);
-            if (PROJ && i >= NPJ && i % 16 == 8 && (i - NPJ) / 16 < kRounds && more) stage_round(A.in2, nxt, 2u * kPlaneB, (i - NPJ) / 16);
+            if (i % 16 == 0 && i / 16 < kRounds && more) stage_round(lds0, wv, A.in, nxt, gnxt, i / 16);
+            if (PROJ && i >= NPJ && i % 16 == 8 && (i - NPJ) / 16 < kRounds && more) stage_round(lds0, wv, A.in2, nxt, 2u * kPlaneB, (i - NPJ) / 16);
             if (PROJ && i == NPJ - 1) {
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();                    // every wave is done with the projection plane
@@ -313,57 +342,16 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
     const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
-
-    auto stage_round = [&](const char* src, int pos, uint32_t off, int r) {   // 4 KB piece r of a position's plane -> LDS
-        glds16(src + (size_t)pos * kPlaneB + threadIdx.x * 16u + r * 4096,
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + off + wv * 1024u + r * 4096u)));
-    };
     int pos = first_position();
     if (pos >= A.batch) return;
-    constexpr uint32_t kZoff = kLds0 + (PROJ ? 3u : 2u) * kPlaneB;      // the zero region follows the planes
-    for (uint32_t u = threadIdx.x; u < kZeroB / 16; u += 256) *reinterpret_cast<uint4*>(smem + kZoff + u * 16) = uint4{0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) stage_round(A.in, pos, 0u, r);
-    if (PROJ) {
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) stage_round(A.in2, pos, 2u * kPlaneB, r);
-    }
+    stage_first<PROJ>(A, smem, lds0, wv, pos);
     bf16x8 W[NS];
-    {
-        const uint4* wp = A.w + ((size_t)wv * NS * 64 + lane);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint4 v = wp[s * 64];
-            __builtin_memcpy(&W[s], &v, 16);
-        }
-    }
     float bias_r[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bias_r[r] = A.bias[32 * wv + 16 * kg + r];
+    load_weights(A, wv, lane, kg, W, bias_r);
     uint32_t lb[4], ob[4], zb[4];
     bool ok[4], edgeL[4], edgeR[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = 32 * j + nn;
-        ok[j] = n < kNPIX;
-        const int nc = ok[j] ? n : 0;
-        const int x = nc % kS;
-        edgeL[j] = x == 0; edgeR[j] = x == kS - 1;
-        lb[j] = kLds0 + (uint32_t)(kg * kPIX + nc + kS - (kS + 1)) * 16u;
-        ob[j] = (uint32_t)(nc + kS) * 16u;
-        zb[j] = kZoff + (lb[j] & 255u);
-    }
-    constexpr int kNVfit = (256 - 4 * DEPTH - AF_TOWER_VSLACK) / 4, kNVmin = NS - (256 - 64) / 4;
-    constexpr int NV = kNVfit > kNVmin ? kNVfit : kNVmin;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        if (s < NV) asm volatile("" : "+v"(W[s]));
-        else asm volatile("" : "+a"(W[s]));
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bias_r[r]));
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    pixel_bases(zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
+    pin_and_sync<NS, DEPTH>(W, bias_r);
 
     // MFMA m of a position -> (pixel tile j, projection step?, k-step index): phase A = m < NH (tiles 0,1), phase B = tiles 2,3
     constexpr int NM = NS * 4, NH = NM / 2, NP = PROJ ? 16 : 0;          // per phase: NH MFMAs of which NP are projection steps
@@ -380,19 +368,19 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
     const f32x16 kZero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     char* o_prev = nullptr;
 
-    // epilogue of pixel-tile pair jp0 as 16 chunks (tile jp0 + (c >> 3), elements 2*(c & 7), +1) of three stages of 3-5 VALU
-    // instructions each — bias + scale | exp2 + clamp - 1 | max, bf16 (+ a 16-byte store after every fourth chunk) — so that one stage
-    // fits the shadow of one MFMA; stage k of chunk c is issued behind MFMA 2*(3c + k) + 3 of the phase, fenced so that hipcc keeps it
-    // there (unfenced it gathers four chunks in front of their store and reads a whole accumulator set in one burst)
+    // epilogue of pixel-tile pair jp0 as 16 chunks (tile jp0 + (c >> 3), elements 2*(c & 7), +1) of kEpiK = 8 stages of TWO
+    // single-issue VALU instructions each — accumulator read + bias, twice | scale + exp2 + clamp, twice | - 1 + max, twice | bf16 |
+    // a 16-byte store after every fourth chunk — so that one stage fits the shadow of one MFMA; stage k of chunk c is issued behind
+    // MFMA 8c + k + 3 of the other pair's phase (128 of its 144 [160]), fenced so that hipcc keeps it there (unfenced it gathers four
+    // chunks in front of their store and reads a whole accumulator set in one burst).  The accumulators are read where they are used:
+    // left to itself hipcc copies the whole finished set out of the accumulator registers in one burst at the top of the phase.
+    // (r4 A/B record, removed from the source: the same epilogue as 16 chunks x 3 stages of 3-5 VALU on 2-vectors — v_pk_add_f32 /
+    //  v_pk_mul_f32 — one stage every second MFMA.  A packed fp32 instruction beside an MFMA costs ~+22-26 cycles of a 32-cycle gap
+    //  (MI355X_MICROARCH.md, "price of one filler beside MFMAs"), i.e. 48 stages x ~20 cycles per phase gave back what hiding the
+    //  epilogue had won (254.5 vs 258.3 us per layer), which is why r5 made the stages scalar.)  Plain v_add / v_mul / v_exp / v_max /
+    // v_cvt_pk_bf16 fillers are hidden up to ~5 per gap.  The opaque asm("" : "+v") after each result keeps hipcc's SLP vectoriser
+    // from re-packing the two elements of a chunk.
     bf16x8 vst;
-    f32x2 ex_[16], et_[16];
-#if AF_TOWER_EPI_SCALAR
-    // r5: the same epilogue as 16 chunks x 8 stages of TWO single-issue VALU instructions, one stage behind every MFMA of the other
-    // pair's phase (128 of its 144 [160]).  r4's stages used 2-vector arithmetic (v_pk_add_f32 / v_pk_mul_f32): a packed fp32
-    // instruction beside an MFMA costs ~+22-26 cycles of a 32-cycle gap (MI355X_MICROARCH.md, "price of one filler beside MFMAs"),
-    // i.e. 48 stages x ~20 cycles per phase gave back what hiding the epilogue had won (254.5 vs 258.3 us per layer).  Plain
-    // v_add / v_mul / v_exp / v_max / v_cvt_pk_bf16 fillers are hidden up to ~5 per gap.  The opaque asm("" : "+v") after each
-    // result keeps hipcc's SLP vectoriser from re-packing the two elements of a chunk.
     float e0_[16], e1_[16], t0_[16], t1_[16];
     auto epi_stage = [&](int jp0, int c, int k, char* o) {
         const int j = jp0 + (c >> 3), q = c & 7, hf = q >> 2, e = 2 * (q & 3);
@@ -427,35 +415,8 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
         }
 #undef AF_OPAQUE
     };
-    (void)ex_; (void)et_;
-#else
-    auto epi_stage = [&](int jp0, int c, int k, char* o) {
-        const int j = jp0 + (c >> 3), q = c & 7, hf = q >> 2, e = 2 * (q & 3);
-        if (k == 0) {
-            // (read where they are used: left to itself hipcc copies the whole finished accumulator set out of the accumulator
-            // registers in one burst of 32 v_accvgpr_read at the top of the phase)
-            float a0, a1;
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(a0) : "a"(acc[j][8 * hf + e]));
-            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(a1) : "a"(acc[j][8 * hf + e + 1]));
-            ex_[c] = f32x2{a0, a1} + f32x2{bias_r[8 * hf + e], bias_r[8 * hf + e + 1]};
-            et_[c] = ex_[c] * 1.44269504088896341f;
-        } else if (k == 1) {
-            f32x2 ee;
-            ee.x = fminf(fmaxf(__builtin_amdgcn_exp2f(et_[c].x), 0.0f), 1.0f);
-            ee.y = fminf(fmaxf(__builtin_amdgcn_exp2f(et_[c].y), 0.0f), 1.0f);
-            et_[c] = ee - 1.0f;
-        } else {
-            vst[e] = (__bf16)fmaxf(ex_[c].x, et_[c].x); vst[e + 1] = (__bf16)fmaxf(ex_[c].y, et_[c].y);
-            if ((q & 3) == 3) {
-                char* dst = o + (uint32_t)((4 * wv + 2 * kg + hf) * kPIX) * 16u + ob[j];
-                if (j == 3) dst = ok[3] ? dst : A.dump + threadIdx.x * 16u;        // (only tile 3 has lanes past the board)
-                *reinterpret_cast<bf16x8*>(dst) = vst;
-            }
-        }
-    };
-#endif
-    constexpr int kEpiK = AF_TOWER_EPI_SCALAR ? 8 : 3;                   // stages per chunk
-    constexpr int kEpiStride = AF_TOWER_EPI_SCALAR ? 1 : 2;              // one stage every kEpiStride MFMAs, from the 4th of a phase on
+    constexpr int kEpiK = 8;                                             // stages per chunk
+    constexpr int kEpiStride = 1;                                        // one stage every kEpiStride MFMAs, from the 4th of a phase on
 
     auto position = [&](auto first_tag, int it, int pos_) {
         constexpr bool FIRST = decltype(first_tag)::value;
@@ -464,18 +425,12 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
         const bool more = nxt < A.batch && !(A.abl & 1);
         char* const o = A.out + (size_t)pos_ * kPlaneB;
         uint32_t bC[4], bL[4], bR[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            bC[j] = (AF_TOWER_ZPAD && !ok[j]) ? zb[j] : gcur + lb[j];
-            bL[j] = edgeL[j] ? zb[j] : bC[j];
-            bR[j] = edgeR[j] ? zb[j] : bC[j];
-        }
+        tap_bases(gcur, lb, zb, ok, edgeL, edgeR, bC, bL, bR);
         auto rd = [&](int m) -> bf16x8 {
             const MI x = mi(m);
-            if (x.proj) return *reinterpret_cast<const bf16x8*>(smem + 2u * kPlaneB + lb[x.j] + (uint32_t)(2 * x.s * kPIX + kS + 1) * 16u);
-            const int t = x.s >> 3, cc = x.s & 7;
-            const uint32_t base = t % 3 == 0 ? bL[x.j] : (t % 3 == 2 ? bR[x.j] : bC[x.j]);
-            return *reinterpret_cast<const bf16x8*>(smem + base + (uint32_t)(2 * cc * kPIX + (t / 3) * kS + (t % 3)) * 16u);
+            if (x.proj) return proj_tap(smem, lb[x.j], x.s);
+            const int t = x.s >> 3;
+            return conv_tap(smem, t % 3 == 0 ? bL[x.j] : (t % 3 == 2 ? bR[x.j] : bC[x.j]), t, x.s & 7);
         };
         bf16x8 ring[DEPTH];
 #pragma unroll
@@ -504,7 +459,7 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
                 }
             }
             // the next position's planes: one 4 KB piece every 16 MFMAs from the start of the position
-            if (m % 16 == 0 && m / 16 < kRounds && more) stage_round(A.in, nxt, gnxt, m / 16);
+            if (m % 16 == 0 && m / 16 < kRounds && more) stage_round(lds0, wv, A.in, nxt, gnxt, m / 16);
             if (PROJ) {
                 constexpr int kAfter = NH + NP;                  // first MFMA after the projection window
                 if (m == kAfter - 1) {
@@ -513,7 +468,7 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (m >= kAfter && (m - kAfter) % 16 == 8 && (m - kAfter) / 16 < kRounds && more)
-                    stage_round(A.in2, nxt, 2u * kPlaneB, (m - kAfter) / 16);
+                    stage_round(lds0, wv, A.in2, nxt, 2u * kPlaneB, (m - kAfter) / 16);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the next position's planes have landed ...
@@ -1104,6 +1059,7 @@ constexpr int64_t kDumpBytes = 4096;                                // TowerArgs
 
 struct af_tower {
     int S = 0, width = 0, blocks = 0, device = 0;
+    int ncu = 0;                    // compute units of `device`: the persistent grid of a convolution launch
     char* arena = nullptr;          // the one allocation: every buffer of the table, the staging area and dump, at 256-byte offsets
     std::vector<char*> buf;         // 4 * blocks + 12 buffers; their addresses never change
     std::vector<char> set;          // per group: its host setter has run
@@ -1178,6 +1134,42 @@ static int g_engine = 3;    // 3 (default, r4): af_tower_conv3 for a block's fir
                             //    4.143 vs 4.167 ms per 8192-position tower pass); 0: af_tower_conv for both; 2: af_tower_conv3 for both (its
                             //    PROJ form is slower: 4.224 ms)
 
+// Every convolution instantiation the library launches: allocate() raises their LDS limit, pick() chooses among them.
+struct ConvKernel {
+    void (*fn)(TowerArgs);
+    bool conv3, proj;       // af_tower_conv3 or af_tower_conv; PROJ = a block's second convolution
+    int depth;              // B-fragment ring
+};
+constexpr ConvKernel kConv[8] = {
+    {af_tower_conv<false, 8>, false, false, 8},   {af_tower_conv<true, 8>, false, true, 8},
+    {af_tower_conv<false, 12>, false, false, 12}, {af_tower_conv<true, 12>, false, true, 12},
+    {af_tower_conv<false, 16>, false, false, 16}, {af_tower_conv<true, 16>, false, true, 16},
+    {af_tower_conv3<false, 8>, true, false, 8},   {af_tower_conv3<true, 8>, true, true, 8},
+};
+
+// The kernel of a block's first or second convolution.  Engine 3: af_tower_conv3 then af_tower_conv, engine 2: af_tower_conv3 for
+// both — at depth 8 whatever key 0 says; engine 0: af_tower_conv at the depth of key 0, or by default the deepest ring that hipcc
+// allocates without scratch, 12 / 8 (a scratch reload's vmcnt(0) would also wait for the LDS-DMA of the next position: measured
+// 400 vs 230 us per launch).
+static const ConvKernel* pick(int engine, bool second, int depth) {
+    const bool conv3 = engine == 2 || (engine == 3 && !second);
+    const int d = engine != 0 ? 8 : depth ? depth : second ? 8 : 12;
+    for (const ConvKernel& k : kConv)
+        if (k.conv3 == conv3 && k.proj == second && k.depth == d) return &k;
+    return nullptr;         // (not reached with the values af_tower_tune accepts)
+}
+
+static TowerArgs layer_args(const af_tower* t, int b, bool second, void* x, void* g, int batch) {
+    TowerArgs a;
+    a.in = static_cast<const char*>(second ? g : x);
+    a.in2 = second ? static_cast<const char*>(x) : nullptr;
+    a.w = t->block<uint4>(b, second ? kW2 : kW1);
+    a.bias = t->block<float>(b, second ? kB2 : kB1);
+    a.out = static_cast<char*>(second ? x : g);
+    a.batch = batch; a.abl = g_abl; a.dump = t->dump;
+    return a;
+}
+
 extern "C" {
 
 int af_tower_tune(int32_t key, int32_t value) {
@@ -1202,11 +1194,9 @@ const char* af_tower_strerror(int code) {
 
 static int allocate(af_tower* t) {
     TW_HIP_OK(hipSetDevice(t->device));
-#define TW_ATTR(P, D) TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv<P, D>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-    TW_ATTR(false, 8); TW_ATTR(true, 8); TW_ATTR(false, 12); TW_ATTR(true, 12); TW_ATTR(false, 16); TW_ATTR(true, 16);
-#undef TW_ATTR
-    TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv3<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(af_tower_conv3<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    TW_HIP_OK(hipDeviceGetAttribute(&t->ncu, hipDeviceAttributeMultiprocessorCount, t->device));
+    for (const ConvKernel& k : kConv)
+        TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int n = 4 * t->blocks + kEnds;
     auto padded = [](int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); };
     size_t total = padded(kStageFloats * 4) + padded(kDumpBytes);
@@ -1334,36 +1324,14 @@ int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_
     if (!t || !x_dev || !g_dev || batch < 1) return AF_TOWER_ERR_ARG;
     for (int b = 0; b < t->blocks; ++b) if (!t->set[b]) return AF_TOWER_ERR_STATE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = 0, ncu = 256;
-    TW_HIP_OK(hipGetDevice(&dev));
-    TW_HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    if (g_grid > 0) ncu = g_grid;
+    const int ncu = g_grid > 0 ? g_grid : t->ncu;
     const int grid = batch < ncu ? batch : ncu;
-    for (int b = 0; b < t->blocks; ++b) {
-        TowerArgs a;
-        a.batch = batch; a.abl = g_abl; a.dump = t->dump;
-        const char* xin = static_cast<const char*>(x_dev);
-        a.in = xin; a.in2 = nullptr; a.w = t->block<uint4>(b, kW1); a.bias = t->block<float>(b, kB1); a.out = static_cast<char*>(g_dev);
-        // ring depth per kernel: the deepest that hipcc allocates without scratch (a scratch reload's vmcnt(0) would
-        // also wait for the LDS-DMA of the next position: measured 400 vs 230 us per launch)
-        const int d1 = g_depth ? g_depth : 12, d2 = g_depth ? g_depth : 8;
-        if (g_engine == 2 || g_engine == 3) {     // r4: epilogue overlapped with the other tile pair's MFMAs (3: first convolution only)
-            hipLaunchKernelGGL((af_tower_conv3<false, 8>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-            a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->block<uint4>(b, kW2); a.bias = t->block<float>(b, kB2);
-            a.out = static_cast<char*>(x_dev);
-            if (g_engine == 2) hipLaunchKernelGGL((af_tower_conv3<true, 8>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
-            else hipLaunchKernelGGL((af_tower_conv<true, 8>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
-            continue;
+    for (int b = 0; b < t->blocks; ++b)
+        for (int second = 0; second < 2; ++second) {
+            const ConvKernel* k = pick(g_engine, second != 0, g_depth);
+            if (!k) return AF_TOWER_ERR_ARG;
+            hipLaunchKernelGGL(k->fn, dim3(grid), dim3(256), lds_bytes(k->proj), st, layer_args(t, b, second != 0, x_dev, g_dev, batch));
         }
-        if (d1 == 16) hipLaunchKernelGGL((af_tower_conv<false, 16>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-        else if (d1 == 12) hipLaunchKernelGGL((af_tower_conv<false, 12>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-        else hipLaunchKernelGGL((af_tower_conv<false, 8>), dim3(grid), dim3(256), kLds0 + 2 * kPlaneB + kZeroB, st, a);
-        a.in = static_cast<const char*>(g_dev); a.in2 = xin; a.w = t->block<uint4>(b, kW2); a.bias = t->block<float>(b, kB2);
-        a.out = static_cast<char*>(x_dev);
-        if (d2 == 16) hipLaunchKernelGGL((af_tower_conv<true, 16>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
-        else if (d2 == 12) hipLaunchKernelGGL((af_tower_conv<true, 12>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
-        else hipLaunchKernelGGL((af_tower_conv<true, 8>), dim3(grid), dim3(256), kLds0 + 3 * kPlaneB + kZeroB, st, a);
-    }
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }

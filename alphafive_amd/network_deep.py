@@ -44,9 +44,8 @@ class _HipEvaluator(object):
             self.net._tower.bind_outputs(policy, value)
 
     def weights_version(self):
-        """What a captured graph of this evaluator is keyed on (SelfPlayEngine.run_ticks_graph): the tower packs its weights
-        once, at select_backend(); every (re)build of the tower bumps the net's pack counter (a monotone count, not id(): CPython
-        may hand a freed tower's id to its successor)."""
+        """What a captured graph of this evaluator is keyed on (SelfPlayEngine.run_ticks_graph): the net's pack counter, which
+        select_backend() and every re-pack of the tower's weights, from the host or on the device, bump."""
         return self.net._pack_version
 
 
@@ -109,21 +108,23 @@ class DeepResNet(object):
 
     def set_variables(self, variables):
         """The host path: values (arrays or tensors, variable_shapes() names and shapes) -> the net's tensors in self.dtype; if a hip
-        backend is selected its tower is rebuilt from them through the host setters (the evaluator handed out stays valid)."""
+        backend is selected the host setters re-pack them into the tower it has, in place (they synchronise the device): the same
+        handle, buffers and bound outputs, so the evaluator handed out and a graph captured over it stay valid."""
         new = {}
         for name in self._checked(variables):
             v = variables[name]
             v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32))
             new[name] = v.to(device=self.device, dtype=self.dtype).contiguous()
         for name, (holder, key, i) in self._named().items():
-            pair = list(holder[key])
-            pair[i] = new[name]
-            holder[key] = tuple(pair)
-        old = getattr(self, "_tower", None)
-        if old is not None:
-            self.select_backend("hip", old.max_batch)
-            self._tower.bind_outputs(old.policy, old.value)         # outputs an engine had bound stay bound
-            old.close()
+            holder[key] = tuple(new[name] if k == i else t for k, t in enumerate(holder[key]))
+        tower = getattr(self, "_tower", None)
+        if tower is not None:
+            for b, blk in enumerate(self.tower):
+                tower.set_block(b, blk)
+            tower.set_stem(self.stem)
+            tower.set_heads(self.vconv, self.pconv)
+            tower.set_dense(self.vfc1 + self.vfc2 + self.pfc)
+            self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     @torch.no_grad()
     def set_variables_device(self, tensors):
@@ -190,9 +191,8 @@ class DeepResNet(object):
             raise ValueError(name)
         from . import tower_hip
         self._pack_version = getattr(self, "_pack_version", 0) + 1
-        self._tower = tower_hip.HipTower(self.tower, self.board_size, self.width, max_batch, self.device,
-                                         stem=self.stem, vconv=self.vconv, pconv=self.pconv,
-                                         dense=(self.vfc1[0], self.vfc1[1], self.vfc2[0], self.vfc2[1], self.pfc[0], self.pfc[1]))
+        self._tower = tower_hip.HipTower(self.tower, self.board_size, self.width, max_batch, self.device, stem=self.stem,
+                                         vconv=self.vconv, pconv=self.pconv, dense=self.vfc1 + self.vfc2 + self.pfc)
         return _HipEvaluator(self)
 
     @torch.no_grad()

@@ -28,8 +28,9 @@ S, W, NPIX = 11, 128, 121
 NPOS = 128                       # positions the block generators provide (the tests take the first B)
 NDIST = 64                       # distinct positions of the stem / heads / dense generators (larger batches tile them)
 ISOLATIONS = ("conv1", "conv2", "proj")
-# (engine = tune key 3, ring depth = tune key 0): af_tower_conv3 + af_tower_conv, af_tower_conv3 for both, af_tower_conv<*, depth>
-ENGINES = ((3, 0), (2, 0), (0, 0), (0, 8), (0, 12), (0, 16))
+# (engine = tune key 3, ring depth = tune key 0): af_tower_conv3 + af_tower_conv, af_tower_conv3 for both, af_tower_conv<*, depth>;
+# engines 3 and 2 run at depth 8 whatever key 0 says: (3, 16) and (2, 12) pin that a depth is neither refused nor honoured there
+ENGINES = ((3, 0), (2, 0), (0, 0), (0, 8), (0, 12), (0, 16), (3, 16), (2, 12))
 # (batch, persistent workgroups = tune key 1).  Default grid min(batch, CUs): a multiple of 8 (XCD swizzle on) at 8 and 128 only.
 # 121 positions on 3 / 8 / 16 workgroups: 41 / 16 / 8 iterations each, both LDS buffer parities, ragged last passes.
 # 9 / 17 / 25 positions on 8 workgroups: workgroup 0 runs 2 / 3 / 4 positions, the others one fewer — af_tower_conv3's

@@ -451,6 +451,52 @@ def test_refusals_change_nothing(sets, refs):
         nodense.close()
 
 
+def test_set_variables_repacks_the_tower_in_place(sets, monkeypatch):
+    """DeepResNet.set_variables, the host path, on a net with a hip backend: the host setters on the tower it has — no new handle,
+    the engine's bound outputs stay bound — and the bits of a fresh net that got the same weights before select_backend."""
+    import torch
+    from alphafive_amd import tower_hip
+    from alphafive_amd.network_deep import DeepResNet
+    made = []
+    real_init = tower_hip.HipTower.__init__
+
+    def counting_init(self, *a, **kw):
+        made.append(self)
+        real_init(self, *a, **kw)
+    monkeypatch.setattr(tower_hip.HipTower, "__init__", counting_init)
+
+    deep = DeepResNet(S, blocks=BLOCKS, width=W, device="cuda", seed=7)
+    pv = deep.select_backend("hip", MAXB)
+    first = deep._tower
+    policy, value = torch.zeros((MAXB, S * S), device="cuda"), torch.zeros(MAXB, device="cuda")
+    pv.bind_outputs(policy, value)
+    x = planes(MAXB)
+    before = tuple(t.clone() for t in pv(x))
+    version = pv.weights_version()
+    try:
+        deep.set_variables(sets["V1"])
+        assert deep._tower is first and len(made) == 1                      # re-packed in place: no new handle
+        assert pv.weights_version() == version + 1
+        assert first.policy is policy and first.value is value
+        policy.zero_()
+        value.zero_()
+        p, v = pv(x)
+        assert p.data_ptr() == policy.data_ptr() and v.data_ptr() == value.data_ptr()
+        got = (policy.clone(), value.clone())
+        assert not torch.equal(got[0], before[0]) and not torch.equal(got[1], before[1])       # the outputs move
+        fresh = DeepResNet(S, blocks=BLOCKS, width=W, device="cuda", seed=99)
+        fresh.set_variables(sets["V1"])
+        assert len(made) == 1                                               # (no backend yet: nothing to re-pack)
+        try:
+            ref = tuple(t.clone() for t in fresh.select_backend("hip", MAXB)(x))
+        finally:
+            if getattr(fresh, "_tower", None) is not None:
+                fresh._tower.close()
+        assert same_bits(got, ref)
+    finally:
+        first.close()
+
+
 def test_live_trainer_drives_the_evaluator(monkeypatch):
     """A deep Trainer on the device, three steps; after each the evaluator takes the parameters without the host and must give the
     bits of a fresh DeepResNet that got trainer.variables() through the host path."""
