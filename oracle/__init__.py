@@ -15,7 +15,7 @@ _LIB = os.path.join(_HERE, "libaf_oracle.so")
 
 RNG_MT, RNG_PHILOX = 0, 1
 PV_PSEUDO, PV_CALLBACK = 0, 1
-STATE_CAP = 272
+STATE_CAP = 288            # af_oracle.h AFO_STATE_CAP: a full 16x16 board is 272 characters + NUL
 
 
 class Config(C.Structure):

@@ -605,7 +605,7 @@ int afo_run(afo_player* P, int max_T, char* states, float* policies, int* last_c
     const int C = P->C;
     int8_t board[AFO_MAXC];
     memset(board, 0, sizeof(board));
-    char state[272];
+    char state[AFO_STATE_CAP];
     afo_board_to_state(board, P->S, state, sizeof(state));       /* == get_init_state :37-46 */
     int T = 0, last = -1, over = 0;
     double value = 0.0;
@@ -615,7 +615,7 @@ int afo_run(afo_player* P, int max_T, char* states, float* policies, int* last_c
         int rc = afo_get_action(P, state, last, 0, policies + (size_t)T * C, &action, visits + (size_t)T * C);
         if (rc < 0) return rc;
         if (rc == 1) memset(policies + (size_t)T * C, 0, sizeof(float) * (size_t)C);
-        memcpy(states + (size_t)T * 272, state, 272);
+        memcpy(states + (size_t)T * AFO_STATE_CAP, state, AFO_STATE_CAP);
         last_cells[T] = last; action_cells[T] = action;
         ++T;
         afo_state_to_board(state, P->S, board);

@@ -79,7 +79,9 @@ int  afo_tree_dump_w64(const afo_player* p, int cap, double* w);
 int afo_get_action(afo_player* p, const char* state, int last_cell, int random_a,
                    float* policy_out, int* action_cell, int32_t* visits_out);
 
-/* player.py:53 run.  Arrays sized for max_T plies.  states: max_T x 272 chars.
+/* A state string (utils.py:156-175) with its NUL: a full 16x16 board is 256 stones + 16 '/' = 272 characters. */
+#define AFO_STATE_CAP 288
+/* player.py:53 run.  Arrays sized for max_T plies.  states: max_T x AFO_STATE_CAP chars.
  * Returns T (>0) or <0 on error. final_value is is_game_over's value at the end. */
 int afo_run(afo_player* p, int max_T, char* states, float* policies, int* last_cells,
             int* action_cells, int32_t* visits, double* values, float* weights, double* final_value);
