@@ -1,7 +1,8 @@
 // af_tower_bf16.hip — bf16 residual tower for gfx950 (C ABI: include/af_tower_bf16.h).
 //
-// Two kernels, af_tower_conv<PROJ, DEPTH> and af_tower_conv3<PROJ, DEPTH>, compute the same 3x3 convolution 128 -> 128 over
-// 11x11 boards as an implicit GEMM
+// Two kernels, af_tower_conv<G, PROJ, DEPTH> and af_tower_conv3<G, PROJ, DEPTH>, compute the same 3x3 convolution 128 -> 128 over
+// 11x11 boards (G = Geo<11>; what follows describes that geometry — Geo<15>, which af_tower_conv alone runs, on half boards, is
+// described at the geometry types) as an implicit GEMM
 //   out[cout][pixel] = sum_{tap, cin} W[cout][cin][tap] * in[cin][pixel + tap offset]
 // on v_mfma_f32_32x32x16_bf16 (M = 32 couts, N = 32 pixels, K = 16 cin of one tap), plus, for the second
 // convolution of a block (PROJ), 8 more k-steps that fold the block's 1x1 projection of the block input in.
@@ -98,11 +99,53 @@ struct TowerArgs {
     char* dump;          // af_tower_conv3: 4 KB the lanes past the board store to (an unconditional store keeps the epilogue out of a branch)
 };
 
-constexpr int kS = 11, kPIX = 144, kNPIX = kS * kS;                    // 13 rows x 11 pixels (+1): pixel n sits at unit n + 11
-constexpr uint32_t kPlaneB = 16u * kPIX * 16u;                          // 36,864 bytes per position
-constexpr int kRounds = kPlaneB / (256 * 16);                           // 9 LDS-DMA rounds of 256 lanes x 16 B
+// Board geometry: every size below is a compile-time member of Geo<S> (as in af_conv_f16s.hip); the host forks once, in with_geo.
+//   11x11: a position is one unit of work.  Its plane is 13 rows x 11 pixels (+1) = 144 units per channel octet, pixel n at unit
+//          n + 11, and goes to LDS as it lies in memory: 9 LDS-DMA rounds of 256 lanes x 16 B.
+//   15x15: 225 pixels are 8 pixel tiles and a 64-KB plane — neither the four accumulator sets nor three planes in LDS hold a whole
+//          position — so the convolution runs every board as HALVES = 2 pseudo-positions: half 0 computes board rows 0..7 (120
+//          pixels), half 1 rows 8..14 (105).  A half stages its rows plus one above and one below: 10 rows = 150 units per octet
+//          from unit 120 * half of the 256-unit plane (half 1: the 135 units up to the plane's last row, the bottom zero row), gathered
+//          by the per-lane addresses of the LDS-DMA into one contiguous half-plane of LPIX = 160 units per octet (a kg stride that
+//          is a multiple of 128 B, as 144 is): 10 rounds.  Inside a half-plane pixel n of the half sits at unit n + 15, exactly as
+//          pixel n sits at unit n + 11 above, so the tap addresses are the same expressions.
+//          Stem, heads and dense layers work on whole positions: 8 pixel / output tiles.
 constexpr uint32_t kLds0 = 256u;                                        // planes start here: unit -1 of a plane stays inside LDS
-constexpr uint32_t kZeroB = 33024u;                                     // all-zero LDS region the edge lanes read instead of a wrapped neighbour
+template <int S_> struct Geo;
+template <> struct Geo<11> {
+    static constexpr int S = 11, NPIX = 121, HALVES = 1;
+    static constexpr int PIX = 144, LPIX = 144;                         // units per channel octet: in memory, in LDS
+    static constexpr int HPIX0 = 121, HPIX1 = 121, HOFF = 0;            // pixels of half 0 / 1; plane unit where half 1 starts
+    static constexpr int LIVE0 = 144, LIVE1 = 144;                      // units per octet a half stages
+    static constexpr uint32_t kZeroB = 33024u;                          // all-zero LDS region the edge lanes read instead of a wrapped neighbour
+    static constexpr int NT = 4;                                        // 32-pixel tiles of a whole position (= 32-output tiles of the policy)
+    static constexpr int KP = 121, KV = 31, KVPAD = 496;                // k-steps of the policy / value-fc1 dense layers
+};
+template <> struct Geo<15> {
+    static constexpr int S = 15, NPIX = 225, HALVES = 2;
+    static constexpr int PIX = 256, LPIX = 160;
+    static constexpr int HPIX0 = 120, HPIX1 = 105, HOFF = 120;
+    static constexpr int LIVE0 = 150, LIVE1 = 135;
+    static constexpr uint32_t kZeroB = (14u * 160u + 2u * 15u + 2u) * 16u + 272u;    // 36,624: the largest tap offset + a lane's bank offset + one unit
+    static constexpr int NT = 8;
+    static constexpr int KP = 225, KV = 57, KVPAD = 912;
+};
+template <class G> struct Lay {
+    static constexpr uint32_t kPlaneB = 16u * G::PIX * 16u;             // bytes per position in memory: 36,864 / 65,536
+    static constexpr uint32_t kPlaneL = 16u * G::LPIX * 16u;            // bytes per (half-)plane in LDS: 36,864 / 40,960
+    static constexpr int kRounds = kPlaneL / (256 * 16);                // 9 / 10 LDS-DMA rounds of 256 lanes x 16 B
+    static constexpr uint32_t zero_off(bool proj) { return kLds0 + (proj ? 3u : 2u) * kPlaneL; }      // LDS: [256 B][g0][g1]([h])[zero region]
+    static constexpr uint32_t lds_bytes(bool proj) { return zero_off(proj) + G::kZeroB; }            // a launch's dynamic LDS
+    static_assert(kPlaneL % 4096 == 0 && G::kZeroB % 16 == 0, "whole LDS-DMA rounds, whole zero units");
+    static_assert(lds_bytes(true) <= 160u * 1024u, "a gfx950 workgroup has 163,840 bytes of LDS");
+    // the farthest unit a lane can form inside a plane — past-board lanes included (they keep pixel 0's base for the projection tap):
+    // channel octet 15 (kg = 1, cc = 7), the last pixel of the larger half, tap (2, 2) — is still inside that plane
+    static_assert((G::LPIX + G::HPIX0 - 2) + 14 * G::LPIX + 2 * G::S + 2 < 16 * G::LPIX, "largest tap offset against the end of the plane");
+    // ... and the farthest one inside the zero region: bank offset (< 256) + the largest tap offset + the 16 bytes read
+    static_assert(255u + (14u * G::LPIX + 2u * G::S + 2u) * 16u + 16u <= G::kZeroB, "largest tap offset against the end of the zero region");
+    static_assert(G::HPIX0 <= 128 && G::HPIX1 <= 128 && G::HPIX0 >= G::HPIX1, "a half fits four pixel tiles");
+    static_assert(G::HOFF + G::LIVE1 <= G::PIX && G::LIVE0 <= G::LPIX, "what a half stages lies inside the plane");
+};
 
 #ifdef AF_TOWER_TIMING
 // profiling build only (tools/probe_tower_timing.py): per wave and position, cycles of MFMA loop | wait for the next planes | barrier | epilogue
@@ -117,25 +160,34 @@ __device__ unsigned long long g_tower_cyc[2][256][4][5];
 // af_tower_conv3's steady-state MFMA blocks (+2 to +8 v_accvgpr_read_b32 per 16-MFMA block: profiles/tower_conv_shared_setup.md).
 // lane, kg = lane >> 5 and nn = lane & 31 are the kernel's, computed at its top (derived again in here they cost registers) ----
 
-constexpr uint32_t zero_off(bool proj) { return kLds0 + (proj ? 3u : 2u) * kPlaneB; }   // LDS: [256 B][g0][g1]([h])[zero region]
-constexpr uint32_t lds_bytes(bool proj) { return zero_off(proj) + kZeroB; }             // a launch's dynamic LDS
-
-// 4 KB piece r of a position's plane -> LDS at byte offset off behind lds0 (wave wv's 1 KB of it)
+// 4 KB piece r of a position's plane -> LDS at byte offset off behind lds0 (wave wv's 1 KB of it).  HALVES = 2: pos is a
+// pseudo-position (board pos >> 1, half pos & 1) and the piece is gathered: LDS unit u = 256 r + thread = (octet u / LPIX, unit w of
+// the half-plane) comes from plane unit HOFF * half + w of that octet.  The LDS-DMA writes all 256 units of a piece whatever the
+// lane's address, so a lane whose unit the half does not stage (w >= LIVE: the pad of the half-plane, and half 1's tenth row,
+// which would lie past the plane) re-reads the half's first unit; no tap of a live pixel reaches those units.
+template <class G>
 __device__ __forceinline__ void stage_round(uint32_t lds0, uint32_t wv, const char* src, int pos, uint32_t off, int r) {
-    const char* gp = src + (size_t)pos * kPlaneB + threadIdx.x * 16u + r * 4096;
+    const char* gp;
+    if constexpr (G::HALVES == 1) {
+        gp = src + (size_t)pos * Lay<G>::kPlaneB + threadIdx.x * 16u + r * 4096;
+    } else {
+        const uint32_t half = (uint32_t)pos & 1u, u = (uint32_t)r * 256u + threadIdx.x, oct = u / (uint32_t)G::LPIX, w = u - oct * G::LPIX;
+        const uint32_t wl = w < (half ? (uint32_t)G::LIVE1 : (uint32_t)G::LIVE0) ? w : 0u;
+        gp = src + (size_t)(pos >> 1) * Lay<G>::kPlaneB + (oct * G::PIX + half * G::HOFF + wl) * 16u;
+    }
     const uint32_t ld = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0 + off + wv * 1024u + r * 4096u));
     glds16(gp, ld);
 }
 
 // the zero region, and the planes of the workgroup's first position on their way
-template <bool PROJ>
+template <class G, bool PROJ>
 __device__ __forceinline__ void stage_first(const TowerArgs& A, char* smem, uint32_t lds0, uint32_t wv, int pos) {
-    for (uint32_t u = threadIdx.x; u < kZeroB / 16; u += 256) *reinterpret_cast<uint4*>(smem + zero_off(PROJ) + u * 16) = uint4{0, 0, 0, 0};
+    for (uint32_t u = threadIdx.x; u < G::kZeroB / 16; u += 256) *reinterpret_cast<uint4*>(smem + Lay<G>::zero_off(PROJ) + u * 16) = uint4{0, 0, 0, 0};
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) stage_round(lds0, wv, A.in, pos, 0u, r);
+    for (int r = 0; r < Lay<G>::kRounds; ++r) stage_round<G>(lds0, wv, A.in, pos, 0u, r);
     if (PROJ) {
 #pragma unroll
-        for (int r = 0; r < kRounds; ++r) stage_round(lds0, wv, A.in2, pos, 2u * kPlaneB, r);
+        for (int r = 0; r < Lay<G>::kRounds; ++r) stage_round<G>(lds0, wv, A.in2, pos, 2u * Lay<G>::kPlaneL, r);
     }
 }
 
@@ -156,17 +208,18 @@ __device__ __forceinline__ void load_weights(const TowerArgs& A, uint32_t wv, in
 // stored back to back (no pad columns: consecutive lanes read consecutive 16-byte units, which is what keeps
 // ds_read_b128 conflict-free); for the left / right taps of the first / last pixel of a row the lane reads zeros
 // from a dedicated LDS region (a different base register, no per-read VALU).
+template <class G>
 __device__ __forceinline__ void pixel_bases(uint32_t zoff, int kg, int nn, uint32_t (&lb)[4], uint32_t (&ob)[4], uint32_t (&zb)[4],
                                             bool (&ok)[4], bool (&edgeL)[4], bool (&edgeR)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int n = 32 * j + nn;
-        ok[j] = n < kNPIX;
+        ok[j] = n < G::HPIX0;                                           // (HALVES = 2: half 1 has fewer, see the position loop)
         const int nc = ok[j] ? n : 0;
-        const int x = nc % kS;
-        edgeL[j] = x == 0; edgeR[j] = x == kS - 1;
-        lb[j] = kLds0 + (uint32_t)(kg * kPIX + nc + kS - (kS + 1)) * 16u;
-        ob[j] = (uint32_t)(nc + kS) * 16u;                              // output unit of the pixel
+        const int x = nc % G::S;
+        edgeL[j] = x == 0; edgeR[j] = x == G::S - 1;
+        lb[j] = kLds0 + (uint32_t)(kg * G::LPIX + nc + G::S - (G::S + 1)) * 16u;
+        ob[j] = (uint32_t)(nc + G::S) * 16u;                            // output unit of the pixel (HALVES = 2: behind the half's first unit)
         zb[j] = zoff + (lb[j] & 255u);                                  // same banks as the lane's own unit: stays conflict-free
     }
 }
@@ -205,44 +258,61 @@ __device__ __forceinline__ void tap_bases(uint32_t gcur, const uint32_t (&lb)[4]
 }
 
 // B fragment of projection k-step cc (block-input plane, the pixel itself) ...
+template <class G>
 __device__ __forceinline__ bf16x8 proj_tap(const char* smem, uint32_t lbj, int cc) {
-    return *reinterpret_cast<const bf16x8*>(smem + 2u * kPlaneB + lbj + (uint32_t)(2 * cc * kPIX + kS + 1) * 16u);
+    return *reinterpret_cast<const bf16x8*>(smem + 2u * Lay<G>::kPlaneL + lbj + (uint32_t)(2 * cc * G::LPIX + G::S + 1) * 16u);
 }
 // ... and of tap t (0..8, row-major), cin step cc of the 3x3 convolution, from the base of the tap's column: bL / bC / bR for
 // t % 3 = 0 / 1 / 2.  The caller picks the column with a conditional of its own: with that choice in here — as a select, through
 // a helper or as a table indexed by t % 3 — hipcc allocates af_tower_conv<true, *> differently (504 -> 496 VGPRs at depth 8, other
 // spills at 12 and 16), and this file's kernels are held to the code they had (profiles/tower_conv_shared_setup.md).
+template <class G>
 __device__ __forceinline__ bf16x8 conv_tap(const char* smem, uint32_t base, int t, int cc) {
-    return *reinterpret_cast<const bf16x8*>(smem + base + (uint32_t)(2 * cc * kPIX + (t / 3) * kS + (t % 3)) * 16u);
+    return *reinterpret_cast<const bf16x8*>(smem + base + (uint32_t)(2 * cc * G::LPIX + (t / 3) * G::S + (t % 3)) * 16u);
 }
 
-// One convolution layer over this workgroup's positions.
-template <bool PROJ, int DEPTH>
+// One convolution layer over this workgroup's (pseudo-)positions.
+// HALVES = 2 and the block's second convolution, which runs in place (out = in2 = the block input x, in = the mid activation g):
+// a half stages rows of x that its sibling half — in another workgroup, or in this one an iteration earlier or later — may already
+// have overwritten: board row 8 for half 0, row 7 for half 1.  That is safe because x is read only through the 1x1 projection, at the
+// half's OWN pixels (proj_tap: the centre unit of rows it computes and nobody else writes); the 3x3 window, which does reach the
+// neighbouring row, reads g, which this launch does not write.  The sibling's row is staged and never multiplied.
+template <class G, bool PROJ, int DEPTH>
 __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
     constexpr int NS = PROJ ? 80 : 72;
     const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
+    using L = Lay<G>;
+    const int npos = G::HALVES == 1 ? A.batch : G::HALVES * A.batch;    // pseudo-positions: board pos >> 1, half pos & 1
     int pos = first_position();
-    if (pos >= A.batch) return;
-    stage_first<PROJ>(A, smem, lds0, wv, pos);
+    if (pos >= npos) return;
+    stage_first<G, PROJ>(A, smem, lds0, wv, pos);
     bf16x8 W[NS];
     float bias_r[16];
     load_weights(A, wv, lane, kg, W, bias_r);
     uint32_t lb[4], ob[4], zb[4];
     bool ok[4], edgeL[4], edgeR[4];
-    pixel_bases(zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
+    pixel_bases<G>(L::zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
     pin_and_sync<NS, DEPTH>(W, bias_r);
 
 #ifdef AF_TOWER_TIMING
     unsigned long long tacc[5] = {0, 0, 0, 0, 0};
 #endif
-    for (int it = 0; pos < A.batch; pos += gridDim.x, ++it) {
-        const uint32_t gcur = (it & 1) ? kPlaneB : 0u, gnxt = kPlaneB - gcur;
+    for (int it = 0; pos < npos; pos += gridDim.x, ++it) {
+        const uint32_t gcur = (it & 1) ? L::kPlaneL : 0u, gnxt = L::kPlaneL - gcur;
         const int nxt = pos + (int)gridDim.x;
-        const bool more = nxt < A.batch && !(A.abl & 1);
+        const bool more = nxt < npos && !(A.abl & 1);
         uint32_t bC[4], bL[4], bR[4];
-        tap_bases(gcur, lb, zb, ok, edgeL, edgeR, bC, bL, bR);
+        bool okh[4];                                                    // HALVES = 2: the lane's pixel exists in THIS half
+        if constexpr (G::HALVES == 1) {
+            tap_bases(gcur, lb, zb, ok, edgeL, edgeR, bC, bL, bR);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) okh[j] = ok[j] && (!(pos & 1) || 32 * j + nn < G::HPIX1);
+            tap_bases(gcur, lb, zb, okh, edgeL, edgeR, bC, bL, bR);
+        }
+        auto live = [&](int j) -> bool { if constexpr (G::HALVES == 1) return ok[j]; else return okh[j]; };
         TT(t0);
         f32x16 acc[4];
 #pragma unroll
@@ -255,9 +325,9 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
         constexpr int NM = NS * 4, NPJ = PROJ ? 32 : 0;
         auto rd = [&](int i) -> bf16x8 {
             const int j = i & 3;
-            if (i < NPJ) return proj_tap(smem, lb[j], i >> 2);
+            if (i < NPJ) return proj_tap<G>(smem, lb[j], i >> 2);
             const int s_ = (i - NPJ) >> 2, t = s_ >> 3;
-            return conv_tap(smem, t % 3 == 0 ? bL[j] : (t % 3 == 2 ? bR[j] : bC[j]), t, s_ & 7);
+            return conv_tap<G>(smem, t % 3 == 0 ? bL[j] : (t % 3 == 2 ? bR[j] : bC[j]), t, s_ & 7);
         };
         bf16x8 ring[DEPTH];
 #pragma unroll
@@ -273,8 +343,8 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
             // the next position's planes are requested one 4 KB piece every 16 MFMAs (an LDS-DMA costs ~5 issue slots:
             // in one burst they would stall the matrix pipe for the whole burst)
-            if (i % 16 == 0 && i / 16 < kRounds && more) stage_round(lds0, wv, A.in, nxt, gnxt, i / 16);
-            if (PROJ && i >= NPJ && i % 16 == 8 && (i - NPJ) / 16 < kRounds && more) stage_round(lds0, wv, A.in2, nxt, 2u * kPlaneB, (i - NPJ) / 16);
+            if (i % 16 == 0 && i / 16 < L::kRounds && more) stage_round<G>(lds0, wv, A.in, nxt, gnxt, i / 16);
+            if (PROJ && i >= NPJ && i % 16 == 8 && (i - NPJ) / 16 < L::kRounds && more) stage_round<G>(lds0, wv, A.in2, nxt, 2u * L::kPlaneL, (i - NPJ) / 16);
             if (PROJ && i == NPJ - 1) {
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();                    // every wave is done with the projection plane
@@ -289,7 +359,9 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
         // epilogue: bias, ELU, bf16, store.  The weight rows are packed so that a lane's 16 accumulator rows are the 16
         // consecutive couts 32*wave + 16*kg + r: two whole 8-channel units = two 16-byte stores per pixel tile, and the
         // 32 lanes of a k half cover 512 contiguous bytes.
-        char* const o = A.out + (size_t)pos * kPlaneB;
+        // (HALVES = 2: the board's full plane, from the half's first unit on — pixel (y, x) lands at unit S * (y + 1) + x)
+        char* const o = G::HALVES == 1 ? A.out + (size_t)pos * L::kPlaneB
+                                       : A.out + (size_t)(pos >> 1) * L::kPlaneB + (uint32_t)((pos & 1) * G::HOFF) * 16u;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -300,7 +372,7 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
                     const f32x2 y = elu2(f32x2{acc[j][8 * hf + e], acc[j][8 * hf + e + 1]} + f32x2{bias_r[8 * hf + e], bias_r[8 * hf + e + 1]});
                     v[e] = (__bf16)y.x; v[e + 1] = (__bf16)y.y;
                 }
-                if (ok[j] && !(A.abl & 2)) *reinterpret_cast<bf16x8*>(o + (uint32_t)((4 * wv + 2 * kg + hf) * kPIX) * 16u + ob[j]) = v;
+                if (live(j) && !(A.abl & 2)) *reinterpret_cast<bf16x8*>(o + (uint32_t)((4 * wv + 2 * kg + hf) * G::PIX) * 16u + ob[j]) = v;
             }
 #ifdef AF_TOWER_TIMING
         { TT(t4); tacc[0] += t1 - t0; tacc[1] += t2 - t1; tacc[2] += t3 - t2; tacc[3] += t4 - t3; tacc[4] += 1; }
@@ -311,10 +383,10 @@ __device__ __forceinline__ void tower_layer(const TowerArgs& A, char* smem) {
 #endif
 }
 
-template <bool PROJ, int DEPTH>
+template <class G, bool PROJ, int DEPTH>
 __global__ __launch_bounds__(256, 1) void af_tower_conv(TowerArgs A) {
     extern __shared__ __attribute__((aligned(16))) char smem[];         // [256 B][g0][g1]([h])
-    tower_layer<PROJ, DEPTH>(A, smem);
+    tower_layer<G, PROJ, DEPTH>(A, smem);
 }
 
 // (r4 A/B record, removed from the source in r6: the whole tower as ONE launch — af_tower_persist, a workgroup keeping its 32 positions
@@ -335,8 +407,12 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv(TowerArgs A) {
 // window (9 pieces, one every 16 MFMAs) with 144 MFMAs to land.  Same MFMAs on the same operands in the same per-accumulator order
 // as af_tower_conv (k-steps ascending per tile; PROJ: projection steps last for tiles 0,1 and first for tiles 2,3 — af_tower_conv
 // runs them first for all four), so tiles 2,3 of the PROJ layers and every tile of the others are bit-identical to af_tower_conv.
-template <bool PROJ, int DEPTH>
+// One position per iteration: instantiated for the geometries with HALVES = 1 only (a 15x15 handle runs af_tower_conv for both).
+template <class G, bool PROJ, int DEPTH>
 __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
+    static_assert(G::HALVES == 1, "af_tower_conv3 walks whole positions");
+    constexpr uint32_t kPlaneB = Lay<G>::kPlaneB;
+    constexpr int kPIX = G::PIX, kRounds = Lay<G>::kRounds;
     extern __shared__ __attribute__((aligned(16))) char smem[];         // [256 B][g0][g1]([h])
     constexpr int NS = PROJ ? 80 : 72;
     const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
@@ -344,13 +420,13 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
     int pos = first_position();
     if (pos >= A.batch) return;
-    stage_first<PROJ>(A, smem, lds0, wv, pos);
+    stage_first<G, PROJ>(A, smem, lds0, wv, pos);
     bf16x8 W[NS];
     float bias_r[16];
     load_weights(A, wv, lane, kg, W, bias_r);
     uint32_t lb[4], ob[4], zb[4];
     bool ok[4], edgeL[4], edgeR[4];
-    pixel_bases(zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
+    pixel_bases<G>(Lay<G>::zero_off(PROJ), kg, nn, lb, ob, zb, ok, edgeL, edgeR);
     pin_and_sync<NS, DEPTH>(W, bias_r);
 
     // MFMA m of a position -> (pixel tile j, projection step?, k-step index): phase A = m < NH (tiles 0,1), phase B = tiles 2,3
@@ -428,9 +504,9 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
         tap_bases(gcur, lb, zb, ok, edgeL, edgeR, bC, bL, bR);
         auto rd = [&](int m) -> bf16x8 {
             const MI x = mi(m);
-            if (x.proj) return proj_tap(smem, lb[x.j], x.s);
+            if (x.proj) return proj_tap<G>(smem, lb[x.j], x.s);
             const int t = x.s >> 3;
-            return conv_tap(smem, t % 3 == 0 ? bL[x.j] : (t % 3 == 2 ? bR[x.j] : bC[x.j]), t, x.s & 7);
+            return conv_tap<G>(smem, t % 3 == 0 ? bL[x.j] : (t % 3 == 2 ? bR[x.j] : bC[x.j]), t, x.s & 7);
         };
         bf16x8 ring[DEPTH];
 #pragma unroll
@@ -459,7 +535,7 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
                 }
             }
             // the next position's planes: one 4 KB piece every 16 MFMAs from the start of the position
-            if (m % 16 == 0 && m / 16 < kRounds && more) stage_round(lds0, wv, A.in, nxt, gnxt, m / 16);
+            if (m % 16 == 0 && m / 16 < kRounds && more) stage_round<G>(lds0, wv, A.in, nxt, gnxt, m / 16);
             if (PROJ) {
                 constexpr int kAfter = NH + NP;                  // first MFMA after the projection window
                 if (m == kAfter - 1) {
@@ -468,7 +544,7 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (m >= kAfter && (m - kAfter) % 16 == 8 && (m - kAfter) / 16 < kRounds && more)
-                    stage_round(lds0, wv, A.in2, nxt, 2u * kPlaneB, (m - kAfter) / 16);
+                    stage_round<G>(lds0, wv, A.in2, nxt, 2u * kPlaneB, (m - kAfter) / 16);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the next position's planes have landed ...
@@ -490,10 +566,10 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
 //  5.37 ms per tower pass against 4.2: its 32-channel slabs give a wave only 36 MFMAs between barriers)
 
 // ---------------------------------------------------------------------------------------------------------------
-// af_tower_stem: the 5x5 stem (3 -> 128, SAME) + bias + ELU, planes fp32 [B][3][11][11] -> C8 bf16, on the same MFMA.
+// af_tower_stem: the 5x5 stem (3 -> 128, SAME) + bias + ELU, planes fp32 [B][3][S][S] -> C8 bf16, on the same MFMA.
 // K = 3 planes x 5 rows x (5 taps padded to 8) = 15 groups of 8 = 8 k-steps; a B fragment (pixel n, group (cin, ky))
 // is the 8-wide input window starting at column x-2 of row y+ky-2, pre-expanded into LDS once per position as
-// 3 x 15 x 11 entries of 8 bf16 ("im2row"), so it is one aligned ds_read_b128.  Weights (8 A fragments) stay in
+// 3 x (S + 4) x S entries of 8 bf16 ("im2row"), so it is one aligned ds_read_b128.  Weights (8 A fragments) stay in
 // registers; workgroups are persistent over positions.
 struct StemArgs {
     const float* planes;
@@ -503,8 +579,15 @@ struct StemArgs {
     int batch;
 };
 
+// Geometry: the image has rows -2..S+1 (SR = S + 4) of IW = S + 5 columns (-2..S+2), an entry row per image row; a wave runs all
+// NT pixel tiles of the position (4 / 8 accumulator sets — 8 weight fragments leave room), a thread loads NL = 2 / 3 of the
+// position's 3 * NPIX plane values.
+template <class G>
 __global__ __launch_bounds__(256) void af_tower_stem_kernel(StemArgs A) {
-    __shared__ __attribute__((aligned(16))) uint4 ent[3 * 15 * kS + 1];      // entry (cin, yy, x) = window x-2..x+5 of row yy-2
+    constexpr int kS = G::S, kNPIX = G::NPIX, kPIX = G::PIX, NT = G::NT, SR = G::S + 4, IW = G::S + 5, NL = (3 * G::NPIX + 255) / 256;
+    constexpr uint32_t kPlaneB = Lay<G>::kPlaneB;
+    static_assert(3 * G::NPIX > 256 && NL <= 3, "plane values per thread");
+    __shared__ __attribute__((aligned(16))) uint4 ent[3 * SR * kS + 1];      // entry (cin, yy, x) = window x-2..x+5 of row yy-2
     const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     bf16x8 W[8];
@@ -516,60 +599,66 @@ __global__ __launch_bounds__(256) void af_tower_stem_kernel(StemArgs A) {
     float bias_r[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) bias_r[r] = A.bias[32 * wv + 16 * kg + r];
-    uint32_t lb[4], ob[4];
-    bool ok[4];
+    uint32_t lb[NT], ob[NT];
+    bool ok[NT];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NT; ++j) {
         const int n = 32 * j + nn;
         ok[j] = n < kNPIX;
         const int nc = ok[j] ? n : 0;
         lb[j] = (uint32_t)nc;                                            // entry index of (cin 0, yy = y, x)
         ob[j] = (uint32_t)(nc + kS) * 16u;
     }
-    // r3 (as in af_stem_mfma_f16s): the planes go through a zero-bordered bf16 image in LDS (rows -2..12, columns -2..13) filled from
+    // r3 (as in af_stem_mfma_f16s): the planes go through a zero-bordered bf16 image in LDS (rows -2..S+1, columns -2..S+2) filled from
     // registers loaded one position ahead; the im2row entries are built from it instead of five scattered global loads each
-    __shared__ __bf16 img[3 * 15 * 16];
-    for (int i = threadIdx.x; i < 3 * 15 * 16; i += 256) img[i] = (__bf16)0.0f;
-    const int t0 = threadIdx.x, t1 = threadIdx.x + 256;
-    const bool h1 = t1 < 3 * kNPIX;
-    auto img_at = [](int i) -> int { const int c = i / kNPIX, p = i - c * kNPIX, y = p / kS, x = p - y * kS; return (c * 15 + y + 2) * 16 + x + 2; };
-    const int a0 = img_at(t0), a1 = img_at(h1 ? t1 : 0);
-    float nx0 = 0.0f, nx1 = 0.0f;
+    __shared__ __bf16 img[3 * SR * IW];
+    for (int i = threadIdx.x; i < 3 * SR * IW; i += 256) img[i] = (__bf16)0.0f;
+    auto img_at = [](int i) -> int { const int c = i / kNPIX, p = i - c * kNPIX, y = p / kS, x = p - y * kS; return (c * SR + y + 2) * IW + x + 2; };
+    int tq[NL], aq[NL];
+    bool hq[NL];
+    float nx[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+        tq[q] = (int)threadIdx.x + 256 * q;
+        hq[q] = q == 0 || tq[q] < 3 * kNPIX;                             // (3 * NPIX > 256: every thread has a first value)
+        aq[q] = img_at(hq[q] ? tq[q] : 0);
+        nx[q] = 0.0f;
+    }
     if ((int)blockIdx.x < A.batch) {
         const float* pl = A.planes + (size_t)blockIdx.x * 3 * kNPIX;
-        nx0 = pl[t0];
-        if (h1) nx1 = pl[t1];
+#pragma unroll
+        for (int q = 0; q < NL; ++q) if (q == 0 || hq[q]) nx[q] = pl[tq[q]];
     }
     for (int pos = blockIdx.x; pos < A.batch; pos += gridDim.x) {
         __syncthreads();                                                 // the previous position's reads are done
-        img[a0] = (__bf16)nx0;
-        if (h1) img[a1] = (__bf16)nx1;
+#pragma unroll
+        for (int q = 0; q < NL; ++q) if (q == 0 || hq[q]) img[aq[q]] = (__bf16)nx[q];
         if (pos + (int)gridDim.x < A.batch) {
             const float* pl = A.planes + (size_t)(pos + gridDim.x) * 3 * kNPIX;
-            nx0 = pl[t0];
-            if (h1) nx1 = pl[t1];
+#pragma unroll
+            for (int q = 0; q < NL; ++q) if (q == 0 || hq[q]) nx[q] = pl[tq[q]];
         }
         __syncthreads();
-        for (int en = threadIdx.x; en < 3 * 15 * kS; en += 256) {
-            const int cin = en / (15 * kS), rem = en - cin * 15 * kS, yy = rem / kS, x = rem - yy * kS;
-            const __bf16* src = img + (cin * 15 + yy) * 16 + x;
+        for (int en = threadIdx.x; en < 3 * SR * kS; en += 256) {
+            const int cin = en / (SR * kS), rem = en - cin * SR * kS, yy = rem / kS, x = rem - yy * kS;
+            const __bf16* src = img + (cin * SR + yy) * IW + x;
             const bf16x8 v = {src[0], src[1], src[2], src[3], src[4], (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
             __builtin_memcpy(&ent[en], &v, 16);
         }
         __syncthreads();
-        f32x16 acc[4];
+        f32x16 acc[NT];
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             // group g = 2s + kg -> (cin, ky); g = 15 is the zero pad of K (its weights are zero: any entry will do)
             const int ga = 2 * s, gb = 2 * s + 1 < 15 ? 2 * s + 1 : 0;
-            const uint32_t offa = (uint32_t)((ga / 5) * 15 + ga % 5) * kS, offb = (uint32_t)((gb / 5) * 15 + gb % 5) * kS;
+            const uint32_t offa = (uint32_t)((ga / 5) * SR + ga % 5) * kS, offb = (uint32_t)((gb / 5) * SR + gb % 5) * kS;
             const uint32_t off = kg ? offb : offa;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < NT; ++j) {
                 bf16x8 b;
                 __builtin_memcpy(&b, &ent[lb[j] + off], 16);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W[s], b, acc[j], 0, 0, 0);
@@ -577,7 +666,7 @@ __global__ __launch_bounds__(256) void af_tower_stem_kernel(StemArgs A) {
         }
         char* const o = A.out + (size_t)pos * kPlaneB;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 bf16x8 v;
@@ -601,7 +690,13 @@ struct HeadsArgs {
     int batch;
 };
 
+// (thread = pixel x half of the couts needs 2 * NPIX <= 256 threads: the geometries with a single half only; a 15x15 handle runs
+//  the MFMA kernel below whatever tune key 4 says)
+template <class G>
 __global__ __launch_bounds__(256) void af_tower_heads_kernel(HeadsArgs A) {
+    static_assert(2 * G::NPIX <= 256, "one thread per pixel and half of the output channels");
+    constexpr int kS = G::S, kNPIX = G::NPIX, kPIX = G::PIX;
+    constexpr uint32_t kPlaneB = Lay<G>::kPlaneB;
     __shared__ __attribute__((aligned(16))) float wl[20 * 128];
     __shared__ float bl[20];
     for (int i = threadIdx.x; i < 20 * 128; i += 256) wl[i] = A.w[i];
@@ -655,9 +750,14 @@ struct HeadsMfmaArgs {
     int batch;
 };
 
+// NT = 8 tiles (15x15): a workgroup is one half of a position's tiles, pseudo-position pp -> position pp >> 1, tiles 4 (pp & 1) + wave;
+// the host launches an even grid there, so a workgroup keeps its half and the lane its pixel.
+template <class G>
 __global__ __launch_bounds__(256) void af_tower_heads_mfma_kernel(HeadsMfmaArgs A) {
+    constexpr int kS = G::S, kNPIX = G::NPIX, kPIX = G::PIX, NH = G::NT / 4;     // workgroups per position
+    constexpr uint32_t kPlaneB = Lay<G>::kPlaneB;
     const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
-    const int j = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // pixel tile
+    const int j = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (NH == 1 ? 0 : 4 * (int)(blockIdx.x & 1));       // pixel tile
     const int p = 32 * j + nn, pc = p < kNPIX ? p : 0;
     bf16x8 W[8];
 #pragma unroll
@@ -667,12 +767,15 @@ __global__ __launch_bounds__(256) void af_tower_heads_mfma_kernel(HeadsMfmaArgs 
     for (int r = 0; r < 16; ++r) bias_r[r] = A.b[16 * kg + r];
     const uint32_t off = (uint32_t)(kg * kPIX + pc + kS) * 16u;                   // the lane's unit inside channel-group plane kg
     uint4 cur[8], nxt[8];
-    int pos = blockIdx.x;
-    if (pos >= A.batch) return;
+    const int npos = NH == 1 ? A.batch : NH * A.batch;
+    auto board = [](int pp) -> int { return NH == 1 ? pp : pp >> 1; };
+    int pp = blockIdx.x;
+    if (pp >= npos) return;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) cur[s] = *reinterpret_cast<const uint4*>(A.x + (size_t)pos * kPlaneB + off + (uint32_t)(2 * s * kPIX) * 16u);
-    for (; pos < A.batch; pos += gridDim.x) {
-        const int np = pos + (int)gridDim.x < A.batch ? pos + (int)gridDim.x : pos;
+    for (int s = 0; s < 8; ++s) cur[s] = *reinterpret_cast<const uint4*>(A.x + (size_t)board(pp) * kPlaneB + off + (uint32_t)(2 * s * kPIX) * 16u);
+    for (; pp < npos; pp += gridDim.x) {
+        const int pos = board(pp);
+        const int np = board(pp + (int)gridDim.x < npos ? pp + (int)gridDim.x : pp);
 #pragma unroll
         for (int s = 0; s < 8; ++s) nxt[s] = *reinterpret_cast<const uint4*>(A.x + (size_t)np * kPlaneB + off + (uint32_t)(2 * s * kPIX) * 16u);
         f32x16 acc;
@@ -720,7 +823,12 @@ struct DenseArgs {
     int batch;
 };
 
+// Geometry: NPIX outputs in NT tiles of 32 (the dead ones carry zero weights and a bias of -1e30), wave w owns the TW = NT / 4 tiles
+// TW w .. TW w + TW - 1, one accumulator set each, on the same B fragment; KP = 16 NPIX / 16 policy k-steps, KV value k-steps.
+template <class G>
 __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
+    constexpr int kNPIX = G::NPIX, NT = G::NT, TW = G::NT / 4, KP = G::KP, KV = G::KV, VIN = 4 * G::NPIX;
+    constexpr int kPinRowB = 16 * G::NPIX * 2, kPinUnits = kPinRowB / 16;      // a policy input row: 3872 / 7200 bytes = 242 / 450 units
     __shared__ float s_red[4][2][32];         // [wave][lane half][position]: partial max / sum / dot
     constexpr int kStageBuf = 32 * 528;
     __shared__ __attribute__((aligned(16))) char s_stage[2 * kStageBuf];      // policy rows of the 32 positions, 16 k-steps at a time
@@ -730,14 +838,16 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
     for (int p0 = blockIdx.x * 32; p0 < A.batch; p0 += gridDim.x * 32) {
         const int pos = p0 + nn < A.batch ? p0 + nn : A.batch - 1;      // dead lanes of a ragged tail recompute the last position
         // ---------------- policy ----------------
-        f32x16 acc;
+        f32x16 acc[TW];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        for (int i = 0; i < TW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
         // B operands through LDS (r4): read straight from global memory a B fragment is one 16-byte piece of a DIFFERENT position's row
         // per lane — 32 rows = 64 cache lines per load instruction; staged, 32 consecutive threads copy 512 contiguous bytes of one row
         // (chunks of 16 k-steps, double buffered, rows 528 bytes apart in LDS: an odd number of 16-byte units, conflict-free
         // ds_read_b128) and the fragment is one LDS read.  A operands (weights, L2) stay on the kRing-deep register ring.  Same k order.
-        constexpr int kRing = 8, kChunks = 8;                                   // 7 x 16 + 9 k-steps
+        constexpr int kRing = 8, kChunks = (KP + 15) / 16;                       // 7 x 16 + 9 k-steps at 11x11, 14 x 16 + 1 at 15x15
         u32x4d stg[4];
         auto stage_load = [&](int c) {
 #pragma unroll
@@ -745,7 +855,7 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
                 const int u = 256 * i + (int)threadIdx.x, row = u >> 5, col = u & 31;
                 const int prw = p0 + row < A.batch ? p0 + row : A.batch - 1;
                 stg[i] = u32x4d{0u, 0u, 0u, 0u};
-                if (32 * c + col < 242) stg[i] = *reinterpret_cast<const u32x4d*>(reinterpret_cast<const char*>(A.pin) + (size_t)prw * 3872 + (size_t)c * 512 + col * 16);
+                if (32 * c + col < kPinUnits) stg[i] = *reinterpret_cast<const u32x4d*>(reinterpret_cast<const char*>(A.pin) + (size_t)prw * kPinRowB + (size_t)c * 512 + col * 16);
             }
         };
         auto stage_store = [&](int buf) {
@@ -755,9 +865,11 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
                 *reinterpret_cast<u32x4d*>(s_stage + buf * kStageBuf + row * 528 + col * 16) = stg[i];
             }
         };
-        u32x4d ra[kRing];
+        u32x4d ra[kRing][TW];
 #pragma unroll
-        for (int q = 0; q < kRing; ++q) ra[q] = *reinterpret_cast<const u32x4d*>(A.wp + ((size_t)q * 4 + wv) * 64 + lane);
+        for (int q = 0; q < kRing; ++q)
+#pragma unroll
+            for (int i = 0; i < TW; ++i) ra[q][i] = *reinterpret_cast<const u32x4d*>(A.wp + ((size_t)q * NT + TW * wv + i) * 64 + lane);
         stage_load(0);
         stage_store(0);
         __syncthreads();
@@ -767,23 +879,29 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int k = 16 * c + q;
-                if (k < 121) {
-                    bf16x8 x, y;
-                    __builtin_memcpy(&x, &ra[q % kRing], 16);
+                if (k < KP) {
+                    bf16x8 y;
                     const u32x4d yb = *reinterpret_cast<const u32x4d*>(bb + q * 32);
                     __builtin_memcpy(&y, &yb, 16);
-                    const int kn = k + kRing < 121 ? k + kRing : 120;          // (past the end: the last step again, never used)
-                    ra[q % kRing] = *reinterpret_cast<const u32x4d*>(A.wp + ((size_t)kn * 4 + wv) * 64 + lane);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0);
+                    const int kn = k + kRing < KP ? k + kRing : KP - 1;        // (past the end: the last step again, never used)
+#pragma unroll
+                    for (int i = 0; i < TW; ++i) {
+                        bf16x8 x;
+                        __builtin_memcpy(&x, &ra[q % kRing][i], 16);
+                        ra[q % kRing][i] = *reinterpret_cast<const u32x4d*>(A.wp + ((size_t)kn * NT + TW * wv + i) * 64 + lane);
+                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc[i], 0, 0, 0);
+                    }
                 }
             }
             if (c + 1 < kChunks) stage_store((c + 1) & 1);
             __syncthreads();
         }
-        // a lane holds the outputs 32*wv + 16*kg + r of position nn (rows permuted at pack time)
+        // a lane holds the outputs 32*(TW*wv + i) + 16*kg + r of position nn (rows permuted at pack time)
         float mx = -3.0e38f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[r] += A.pb[32 * wv + 16 * kg + r]; mx = acc[r] > mx ? acc[r] : mx; }
+        for (int i = 0; i < TW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[i][r] += A.pb[32 * (TW * wv + i) + 16 * kg + r]; mx = acc[i][r] > mx ? acc[i][r] : mx; }
         s_red[wv][kg][nn] = mx;
         __syncthreads();
         float gmx = -3.0e38f;
@@ -794,7 +912,9 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
         __syncthreads();
         float sum = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[r] = __expf(acc[r] - gmx); sum += acc[r]; }
+        for (int i = 0; i < TW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[i][r] = __expf(acc[i][r] - gmx); sum += acc[i][r]; }
         s_red[wv][kg][nn] = sum;
         __syncthreads();
         float gs = 0.0f;
@@ -806,10 +926,12 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
         const float inv = 1.0f / gs;
         if (p0 + nn < A.batch) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int o = 32 * wv + 16 * kg + r;
-                if (o < 121) A.policy[(size_t)pos * 121 + o] = acc[r] * inv;
-            }
+            for (int i = 0; i < TW; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int o = 32 * (TW * wv + i) + 16 * kg + r;
+                    if (o < kNPIX) A.policy[(size_t)pos * kNPIX + o] = acc[i][r] * inv;
+                }
         }
         // ---------------- value ----------------
         float part = 0.0f;
@@ -817,14 +939,14 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
             f32x16 av;
 #pragma unroll
             for (int r = 0; r < 16; ++r) av[r] = 0.0f;
-            const __bf16* vrow = A.vin + (size_t)pos * 484 + 8 * kg;
+            const __bf16* vrow = A.vin + (size_t)pos * VIN + 8 * kg;
             auto load_b = [&](int k) -> u32x4d {
                 u32x4d b = {0u, 0u, 0u, 0u};
-                if (16 * k + 8 * kg + 8 <= 484) b = *reinterpret_cast<const u32x4d*>(vrow + 16 * k);
-                else if (16 * k + 8 * kg < 484) {                          // the last, partial 8-group: 484 = 30*16 + 4
+                if (16 * k + 8 * kg + 8 <= VIN) b = *reinterpret_cast<const u32x4d*>(vrow + 16 * k);
+                else if (16 * k + 8 * kg < VIN) {                          // the last, partial 8-group: 484 = 30*16 + 4, 900 = 56*16 + 4
                     __bf16 t8[8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) t8[e] = 16 * k + 8 * kg + e < 484 ? vrow[16 * k + e] : (__bf16)0.0f;
+                    for (int e = 0; e < 8; ++e) t8[e] = 16 * k + 8 * kg + e < VIN ? vrow[16 * k + e] : (__bf16)0.0f;
                     __builtin_memcpy(&b, t8, 16);
                 }
                 return b;
@@ -835,15 +957,15 @@ __global__ __launch_bounds__(256) void af_tower_dense_kernel(DenseArgs A) {
                 va[q] = *reinterpret_cast<const u32x4d*>(A.wv + ((size_t)q * 2 + wv) * 64 + lane);
                 vb[q] = load_b(q);
             }
-            for (int k0 = 0; k0 < 31; k0 += kRing) {
+            for (int k0 = 0; k0 < KV; k0 += kRing) {
 #pragma unroll
                 for (int q = 0; q < kRing; ++q) {
                     const int k = k0 + q;
-                    if (k < 31) {
+                    if (k < KV) {
                         bf16x8 x, y;
                         __builtin_memcpy(&x, &va[q], 16);
                         __builtin_memcpy(&y, &vb[q], 16);
-                        const int kn = k + kRing < 31 ? k + kRing : 30;
+                        const int kn = k + kRing < KV ? k + kRing : KV - 1;
                         va[q] = *reinterpret_cast<const u32x4d*>(A.wv + ((size_t)kn * 2 + wv) * 64 + lane);
                         vb[q] = load_b(kn);
                         av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, av, 0, 0, 0);
@@ -936,9 +1058,15 @@ __global__ __launch_bounds__(256) void af_tower_pack_blocks_kernel(PackBlocksArg
 // stem, the heads' 1x1 convolutions and the dense layers: the thread index r walks the regions below in order, stem in
 // [0, kPackEndsStem), heads up to kPackEndsHeads, the dense layers in the rest.  A launch covers [first, end): all of it for
 // af_tower_update_device, one group's range for a host setter, which leaves the other groups' pointers null (never reached).
-constexpr int kRowsStem = 4 * 8 * 64, kRowsHeadsA = 8 * 64, kRowsWp = 121 * 4 * 64, kRowsWv = 31 * 2 * 64;
+// Stem and heads are the same for every board size; the dense regions are sized by the geometry (Ends<G>).
+constexpr int kRowsStem = 4 * 8 * 64, kRowsHeadsA = 8 * 64;
 constexpr int kPackEndsStem = kRowsStem + 128, kPackEndsHeads = kPackEndsStem + 20 * 128 + 20 + kRowsHeadsA + 32;
-constexpr int kPackEndsThreads = kPackEndsHeads + kRowsWp + kRowsWv + 121 + 64 + 64 + 1;
+template <class G> struct Ends {
+    static constexpr int kRowsWp = G::KP * G::NT * 64, kRowsWv = G::KV * 2 * 64;    // 121 x 4 / 225 x 8 policy, 31 / 57 value-fc1 fragment sets
+    static constexpr int kPbWords = 32 * G::NT;                                     // policy bias, padded to whole tiles: 128 / 256
+    static constexpr int kThreads = kPackEndsHeads + kRowsWp + kRowsWv + G::NPIX + 64 + 64 + 1;
+    static_assert(16 * G::KP == 16 * G::NPIX && G::KVPAD == 16 * G::KV && G::KVPAD >= 4 * G::NPIX, "k-steps cover the dense layers' inputs");
+};
 struct PackEndsArgs {
     int first, end;
     const float *stem_w, *stem_b, *vconv_w, *vconv_b, *pconv_w, *pconv_b, *vfc1_w, *vfc1_b, *vfc2_w, *vfc2_b, *pfc_w, *pfc_b;
@@ -951,7 +1079,9 @@ struct PackEndsArgs {
     float *o_dense_pb, *o_dense_vb1, *o_dense_vw2, *o_dense_vb2;
 };
 
+template <class G>
 __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A) {
+    constexpr int kRowsWp = Ends<G>::kRowsWp, kRowsWv = Ends<G>::kRowsWv, kNPIX = G::NPIX, NT = G::NT;
     int r = A.first + (int)(blockIdx.x * 256 + threadIdx.x);
     if (r >= A.end) return;
     if (r < kRowsStem) {                         // [wave][k-step][lane]: group g = 2 s + (lane >> 5) = (cin, ky), 5 taps + 3 zeros; g = 15 is zero
@@ -992,31 +1122,31 @@ __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A)
     r -= kRowsHeadsA;
     if (r < 32) { A.o_heads_b32[r] = r < 4 ? A.vconv_b[r] : (r < 20 ? A.pconv_b[r - 4] : 0.0f); return; }
     r -= 32;
-    if (r < kRowsWp) {                           // [k-step][out tile][lane]: pfc [1936][121], outputs 121..127 are zero rows
-        const int lane = r & 63, tile = (r >> 6) & 3, k = r >> 8;                 // k < 121
-        const int o = 32 * tile + pack_perm(lane & 31), ki = 16 * k + 8 * (lane >> 5);    // ki + 7 < 1936
+    if (r < kRowsWp) {                           // [k-step][out tile][lane]: pfc [16 NPIX][NPIX], outputs NPIX..32 NT - 1 are zero rows
+        const int lane = r & 63, tile = (int)((uint32_t)(r >> 6) % NT), k = (int)((uint32_t)(r >> 6) / NT);       // k < KP
+        const int o = 32 * tile + pack_perm(lane & 31), ki = 16 * k + 8 * (lane >> 5);    // ki + 7 < 16 NPIX
         uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        if (o < 121) {
+        if (o < kNPIX) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(A.pfc_w[(size_t)(ki + e) * 121 + o]);
+            for (int e = 0; e < 8; ++e) h[e] = pack_bf16(A.pfc_w[(size_t)(ki + e) * kNPIX + o]);
         }
         A.o_dense_wp[r] = pack_row(h);
         return;
     }
     r -= kRowsWp;
-    if (r < kRowsWv) {                           // [k-step][out tile][lane]: vfc1 [484][64], K padded to 496 with zeros
-        const int lane = r & 63, tile = (r >> 6) & 1, k = r >> 7;                 // k < 31
+    if (r < kRowsWv) {                           // [k-step][out tile][lane]: vfc1 [4 NPIX][64], K padded to KVPAD (496 / 912) with zeros
+        const int lane = r & 63, tile = (r >> 6) & 1, k = r >> 7;                 // k < KV
         const int o = 32 * tile + pack_perm(lane & 31), ki = 16 * k + 8 * (lane >> 5);    // o < 64
         uint32_t h[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            if (ki + e < 484) h[e] = pack_bf16(A.vfc1_w[(size_t)(ki + e) * 64 + o]);
+            if (ki + e < 4 * kNPIX) h[e] = pack_bf16(A.vfc1_w[(size_t)(ki + e) * 64 + o]);
         A.o_dense_wv[r] = pack_row(h);
         return;
     }
     r -= kRowsWv;
-    if (r < 121) { A.o_dense_pb[r] = pack_bf16_f32(A.pfc_b[r]); return; }        // (words 121..127 keep the -1e30 af_tower_create wrote)
-    r -= 121;
+    if (r < kNPIX) { A.o_dense_pb[r] = pack_bf16_f32(A.pfc_b[r]); return; }      // (the words behind keep the -1e30 af_tower_create wrote)
+    r -= kNPIX;
     if (r < 64) { A.o_dense_vb1[r] = pack_bf16_f32(A.vfc1_b[r]); return; }
     r -= 64;
     if (r < 64) { A.o_dense_vw2[r] = pack_bf16_f32(A.vfc2_w[r]); return; }
@@ -1029,10 +1159,21 @@ __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A)
 enum { kW1, kW2, kB1, kB2 };        // w1 / w2: A fragments of a block's two convolutions [wave][s][lane][e], s = 8 tap + cin / 16, then the 1x1 projection
 enum { kStemW, kStemB, kHeadsW, kHeadsB, kHeadsA, kHeadsB32, kDenseWp, kDenseWv, kDensePb, kDenseVb1, kDenseVw2, kDenseVb2, kEnds };
 
-static int64_t buffer_bytes(int i, int blocks) {
+// What the host needs of a geometry, as plain numbers: filled once, in af_tower_create, from Geo<S> (dims_of).
+struct Dims {
+    int S, npix, pix;               // board side, pixels, units per channel octet of the C8 layout
+    int halves;                     // pseudo-positions per board of a convolution launch
+    int rows_wp, rows_wv, pb_words; // the dense regions of the ends packer
+    int ends_threads;
+};
+template <class G> static Dims dims_of() {
+    return Dims{G::S, G::NPIX, G::PIX, G::HALVES, Ends<G>::kRowsWp, Ends<G>::kRowsWv, Ends<G>::kPbWords, Ends<G>::kThreads};
+}
+
+static int64_t buffer_bytes(int i, int blocks, const Dims& d) {
     static const int64_t kBlock[4] = {(int64_t)kRowsW1 * 16, (int64_t)kRowsW2 * 16, 128 * 4, 128 * 4};
-    static const int64_t kEnd[kEnds] = {(int64_t)kRowsStem * 16, 128 * 4, 20 * 128 * 4, 20 * 4, (int64_t)kRowsHeadsA * 16, 32 * 4,
-                                        (int64_t)kRowsWp * 16, (int64_t)kRowsWv * 16, 128 * 4, 64 * 4, 64 * 4, 4};
+    const int64_t kEnd[kEnds] = {(int64_t)kRowsStem * 16, 128 * 4, 20 * 128 * 4, 20 * 4, (int64_t)kRowsHeadsA * 16, 32 * 4,
+                                 (int64_t)d.rows_wp * 16, (int64_t)d.rows_wv * 16, (int64_t)d.pb_words * 4, 64 * 4, 64 * 4, 4};
     return i < 4 * blocks ? kBlock[i % 4] : kEnd[i - 4 * blocks];
 }
 
@@ -1045,20 +1186,28 @@ static int group_of(int i, int blocks) {
 }
 
 // element counts of af_tower_update_device's tensors, in its order (include/af_tower_bf16.h); a host setter takes a run of them
-static int64_t update_count(int i, int blocks) {
+static int64_t update_count(int i, int blocks, const Dims& d) {
     static const int64_t kBlock[6] = {147456, 128, 147456, 128, 16384, 128};
-    static const int64_t kTail[10] = {512, 4, 2048, 16, 30976, 64, 64, 1, 234256, 121};
+    const int64_t C = d.npix;       // vfc1_w [4C][64], pfc_w [16C][C], pfc_b [C]: 30976 / 234256 / 121 at 11, 57600 / 810000 / 225 at 15
+    const int64_t kTail[10] = {512, 4, 2048, 16, 4 * C * 64, 64, 64, 1, 16 * C * C, C};
     if (i == 0) return 9600;
     if (i == 1) return 128;
     if (i < 2 + 6 * blocks) return kBlock[(i - 2) % 6];
     return kTail[i - 2 - 6 * blocks];
 }
 
-constexpr int64_t kStageFloats = 2 * 147456 + 16384 + 3 * 128;      // the largest setter's tensors, a block's six: 1.25 MB
+// the staging area holds the largest setter's tensors, each rounded up to 64 floats: a block's six (1.25 MB) or — 15x15 — the dense six
+static int64_t stage_floats(const Dims& d) {
+    const int64_t r64 = 63, C = d.npix;
+    const int64_t block = 2 * 147456 + 16384 + 3 * 128;
+    const int64_t dense = ((4 * C * 64 + r64) & ~r64) + 3 * 64 + 64 + ((16 * C * C + r64) & ~r64) + ((C + r64) & ~r64);
+    return block > dense ? block : dense;
+}
 constexpr int64_t kDumpBytes = 4096;                                // TowerArgs::dump
 
 struct af_tower {
     int S = 0, width = 0, blocks = 0, device = 0;
+    Dims d = {};
     int ncu = 0;                    // compute units of `device`: the persistent grid of a convolution launch
     char* arena = nullptr;          // the one allocation: every buffer of the table, the staging area and dump, at 256-byte offsets
     std::vector<char*> buf;         // 4 * blocks + 12 buffers; their addresses never change
@@ -1068,6 +1217,10 @@ struct af_tower {
     template <class T> T* block(int b, int k) const { return reinterpret_cast<T*>(buf[4 * b + k]); }
     template <class T> T* end(int k) const { return reinterpret_cast<T*>(buf[4 * blocks + k]); }
 };
+
+// The one fork between the geometries: f(Geo<11>{}) or f(Geo<15>{}) (af_tower_create admits no other size).
+template <class F>
+static int with_geo(const af_tower* t, F&& f) { return t->S == 11 ? f(Geo<11>{}) : f(Geo<15>{}); }
 
 static bool all_set(const af_tower* t) {
     for (char c : t->set) if (!c) return false;
@@ -1097,7 +1250,10 @@ static void pack_ends(const af_tower* t, hipStream_t st, const float* const* src
     a.o_heads_a = t->end<uint4>(kHeadsA); a.o_heads_b32 = t->end<float>(kHeadsB32);
     a.o_dense_wp = t->end<uint4>(kDenseWp); a.o_dense_wv = t->end<uint4>(kDenseWv); a.o_dense_pb = t->end<float>(kDensePb);
     a.o_dense_vb1 = t->end<float>(kDenseVb1); a.o_dense_vw2 = t->end<float>(kDenseVw2); a.o_dense_vb2 = t->end<float>(kDenseVb2);
-    hipLaunchKernelGGL(af_tower_pack_ends_kernel, dim3((end - first + 255) / 256), dim3(256), 0, st, a);
+    with_geo(t, [&](auto g) {
+        hipLaunchKernelGGL(af_tower_pack_ends_kernel<decltype(g)>, dim3((end - first + 255) / 256), dim3(256), 0, st, a);
+        return 0;
+    });
 }
 
 // A host setter, first half: wait for the device (forwards in flight read the buffers), then copy the caller's n fp32 arrays —
@@ -1108,8 +1264,8 @@ static int stage(af_tower* t, int first, int n, const float* const* host, const 
     TW_HIP_OK(hipDeviceSynchronize());
     int64_t at = 0;
     for (int k = 0; k < n; ++k) {
-        const int64_t count = update_count(first + k, t->blocks);
-        if (at + count > kStageFloats) return AF_TOWER_ERR_ARG;         // (no setter's arrays are larger than a block's)
+        const int64_t count = update_count(first + k, t->blocks, t->d);
+        if (at + count > stage_floats(t->d)) return AF_TOWER_ERR_ARG;   // (no setter's arrays are larger than the area)
         TW_HIP_OK(hipMemcpy(t->stage + at, host[k], (size_t)count * 4, hipMemcpyHostToDevice));
         dev[k] = t->stage + at;
         at += (count + 63) & ~(int64_t)63;
@@ -1137,25 +1293,36 @@ static int g_engine = 3;    // 3 (default, r4): af_tower_conv3 for a block's fir
 // Every convolution instantiation the library launches: allocate() raises their LDS limit, pick() chooses among them.
 struct ConvKernel {
     void (*fn)(TowerArgs);
+    int S;                  // board side of the geometry
     bool conv3, proj;       // af_tower_conv3 or af_tower_conv; PROJ = a block's second convolution
     int depth;              // B-fragment ring
+    uint32_t lds;           // dynamic LDS of a launch
 };
-constexpr ConvKernel kConv[8] = {
-    {af_tower_conv<false, 8>, false, false, 8},   {af_tower_conv<true, 8>, false, true, 8},
-    {af_tower_conv<false, 12>, false, false, 12}, {af_tower_conv<true, 12>, false, true, 12},
-    {af_tower_conv<false, 16>, false, false, 16}, {af_tower_conv<true, 16>, false, true, 16},
-    {af_tower_conv3<false, 8>, true, false, 8},   {af_tower_conv3<true, 8>, true, true, 8},
+using G11 = Geo<11>;
+using G15 = Geo<15>;
+constexpr ConvKernel kConv[15] = {
+    {af_tower_conv<G11, false, 8>, 11, false, false, 8, Lay<G11>::lds_bytes(false)},   {af_tower_conv<G11, true, 8>, 11, false, true, 8, Lay<G11>::lds_bytes(true)},
+    {af_tower_conv<G11, false, 12>, 11, false, false, 12, Lay<G11>::lds_bytes(false)}, {af_tower_conv<G11, true, 12>, 11, false, true, 12, Lay<G11>::lds_bytes(true)},
+    {af_tower_conv<G11, false, 16>, 11, false, false, 16, Lay<G11>::lds_bytes(false)}, {af_tower_conv<G11, true, 16>, 11, false, true, 16, Lay<G11>::lds_bytes(true)},
+    {af_tower_conv3<G11, false, 8>, 11, true, false, 8, Lay<G11>::lds_bytes(false)},   {af_tower_conv3<G11, true, 8>, 11, true, true, 8, Lay<G11>::lds_bytes(true)},
+    {af_tower_conv<G15, false, 8>, 15, false, false, 8, Lay<G15>::lds_bytes(false)},   {af_tower_conv<G15, true, 8>, 15, false, true, 8, Lay<G15>::lds_bytes(true)},
+    {af_tower_conv<G15, false, 12>, 15, false, false, 12, Lay<G15>::lds_bytes(false)}, {af_tower_conv<G15, true, 12>, 15, false, true, 12, Lay<G15>::lds_bytes(true)},
+    {af_tower_conv<G15, false, 16>, 15, false, false, 16, Lay<G15>::lds_bytes(false)}, {af_tower_conv<G15, true, 16>, 15, false, true, 16, Lay<G15>::lds_bytes(true)},    {af_tower_conv<G15, true, 6>, 15, false, true, 6, Lay<G15>::lds_bytes(true)},
 };
 
 // The kernel of a block's first or second convolution.  Engine 3: af_tower_conv3 then af_tower_conv, engine 2: af_tower_conv3 for
 // both — at depth 8 whatever key 0 says; engine 0: af_tower_conv at the depth of key 0, or by default the deepest ring that hipcc
 // allocates without scratch, 12 / 8 (a scratch reload's vmcnt(0) would also wait for the LDS-DMA of the next position: measured
 // 400 vs 230 us per launch).
-static const ConvKernel* pick(int engine, bool second, int depth) {
+// 15x15: af_tower_conv for both convolutions whatever the engine (af_tower_conv3 walks whole positions), at the depth of key 0 or,
+// by the same rule, 12 / 6: the gather addresses of the staging rounds cost the PROJ form the registers of a fourth of its ring
+// (depth 8: 36 bytes of scratch; depth 6: none).
+static const ConvKernel* pick(int S, int engine, bool second, int depth) {
+    if (S != 11) engine = 0;
     const bool conv3 = engine == 2 || (engine == 3 && !second);
-    const int d = engine != 0 ? 8 : depth ? depth : second ? 8 : 12;
+    const int d = engine != 0 ? 8 : depth ? depth : !second ? 12 : S == 11 ? 8 : 6;
     for (const ConvKernel& k : kConv)
-        if (k.conv3 == conv3 && k.proj == second && k.depth == d) return &k;
+        if (k.S == S && k.conv3 == conv3 && k.proj == second && k.depth == d) return &k;
     return nullptr;         // (not reached with the values af_tower_tune accepts)
 }
 
@@ -1199,24 +1366,26 @@ static int allocate(af_tower* t) {
         TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int n = 4 * t->blocks + kEnds;
     auto padded = [](int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); };
-    size_t total = padded(kStageFloats * 4) + padded(kDumpBytes);
-    for (int i = 0; i < n; ++i) total += padded(buffer_bytes(i, t->blocks));
+    const int64_t stage_bytes = stage_floats(t->d) * 4;
+    size_t total = padded(stage_bytes) + padded(kDumpBytes);
+    for (int i = 0; i < n; ++i) total += padded(buffer_bytes(i, t->blocks, t->d));
     { void* q = nullptr; TW_HIP_OK(hipMalloc(&q, total)); t->arena = static_cast<char*>(q); }
     char* p = t->arena;
-    for (int i = 0; i < n; ++i) { t->buf.push_back(p); p += padded(buffer_bytes(i, t->blocks)); }
-    t->stage = reinterpret_cast<float*>(p); p += padded(kStageFloats * 4);
+    for (int i = 0; i < n; ++i) { t->buf.push_back(p); p += padded(buffer_bytes(i, t->blocks, t->d)); }
+    t->stage = reinterpret_cast<float*>(p); p += padded(stage_bytes);
     t->dump = p;
     t->set.assign(t->blocks + kEndGroups, 0);
-    // dense_pb's words 121..127 — policy outputs that do not exist — are -1e30 for good: no packer writes them
-    const float tail[7] = {-1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f, -1.0e30f};
-    TW_HIP_OK(hipMemcpy(t->end<float>(kDensePb) + 121, tail, sizeof(tail), hipMemcpyHostToDevice));
+    // dense_pb's words behind the last pixel (121..127 / 225..255) — policy outputs that do not exist — are -1e30 for good: no packer writes them
+    const std::vector<float> tail(t->d.pb_words - t->d.npix, -1.0e30f);
+    TW_HIP_OK(hipMemcpy(t->end<float>(kDensePb) + t->d.npix, tail.data(), tail.size() * sizeof(float), hipMemcpyHostToDevice));
     return AF_TOWER_OK;
 }
 
 int af_tower_create(int32_t S, int32_t width, int32_t blocks, int32_t device, af_tower** out) {
-    if (!out || S != kS || width != 128 || blocks < 1) return AF_TOWER_ERR_ARG;
+    if (!out || (S != 11 && S != 15) || width != 128 || blocks < 1) return AF_TOWER_ERR_ARG;
     af_tower* t = new af_tower();
     t->S = S; t->width = width; t->blocks = blocks; t->device = device;
+    with_geo(t, [&](auto g) { t->d = dims_of<decltype(g)>(); return 0; });
     const int rc = allocate(t);
     if (rc) { af_tower_destroy(t); return rc; }
     *out = t;
@@ -1269,7 +1438,7 @@ int af_tower_set_dense(af_tower* t, const float* vfc1_w, const float* vfc1_b, co
     const float* dev[12] = {};
     const int rc = stage(t, 2 + 6 * t->blocks + 4, 6, host, dev + 6);
     if (rc) return rc;
-    pack_ends(t, nullptr, dev, kPackEndsHeads, kPackEndsThreads);
+    pack_ends(t, nullptr, dev, kPackEndsHeads, t->d.ends_threads);
     return packed(t, t->blocks + kDense);
 }
 
@@ -1283,7 +1452,10 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
     a.vb1 = t->end<float>(kDenseVb1); a.vw2 = t->end<float>(kDenseVw2); a.vb2 = t->end<float>(kDenseVb2);
     a.policy = policy_dev; a.value = value_dev; a.batch = batch;
     const int blocks = (batch + 31) / 32;
-    hipLaunchKernelGGL(af_tower_dense_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    with_geo(t, [&](auto g) {
+        hipLaunchKernelGGL(af_tower_dense_kernel<decltype(g)>, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+        return 0;
+    });
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
@@ -1294,7 +1466,10 @@ int af_tower_stem(af_tower* t, void* stream, const float* planes_dev, void* x_de
     StemArgs a;
     a.planes = planes_dev; a.w = t->end<uint4>(kStemW); a.bias = t->end<float>(kStemB); a.out = static_cast<char*>(x_dev); a.batch = batch;
     const int grid = batch < 1024 ? batch : 1024;
-    hipLaunchKernelGGL(af_tower_stem_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    with_geo(t, [&](auto g) {
+        hipLaunchKernelGGL(af_tower_stem_kernel<decltype(g)>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+        return 0;
+    });
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
@@ -1306,31 +1481,37 @@ int af_tower_heads(af_tower* t, void* stream, const void* x_dev, void* vin_dev, 
     a.x = static_cast<const char*>(x_dev); a.w = t->end<float>(kHeadsW); a.b = t->end<float>(kHeadsB);
     a.vin = static_cast<__bf16*>(vin_dev); a.pin = static_cast<__bf16*>(pin_dev); a.batch = batch;
     const int grid = batch < 2048 ? batch : 2048;
-    if (g_heads == 0) {
-        hipLaunchKernelGGL(af_tower_heads_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    if (g_heads == 0 && t->S == 11) {                // (the VALU kernel exists at 11x11 only: key 4 has no effect on a 15x15 handle)
+        hipLaunchKernelGGL(af_tower_heads_kernel<G11>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     } else {
         HeadsMfmaArgs m;
         m.x = a.x; m.a = t->end<uint4>(kHeadsA); m.b = t->end<float>(kHeadsB32); m.vin = a.vin; m.pin = a.pin; m.batch = batch;
-        hipLaunchKernelGGL(af_tower_heads_mfma_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), m);
+        // 15x15: two workgroups per position, and an even grid, so that a workgroup keeps its half of the tiles
+        with_geo(t, [&](auto g) {
+            using G = decltype(g);
+            hipLaunchKernelGGL(af_tower_heads_mfma_kernel<G>, dim3(grid * (G::NT / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), m);
+            return 0;
+        });
     }
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
 
-int32_t af_tower_pix(const af_tower*) { return kPIX; }
-int64_t af_tower_plane_elems(const af_tower*) { return (int64_t)128 * kPIX; }
+int32_t af_tower_pix(const af_tower* t) { return t ? t->d.pix : 0; }
+int64_t af_tower_plane_elems(const af_tower* t) { return t ? (int64_t)128 * t->d.pix : 0; }
 
 int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch) {
     if (!t || !x_dev || !g_dev || batch < 1) return AF_TOWER_ERR_ARG;
     for (int b = 0; b < t->blocks; ++b) if (!t->set[b]) return AF_TOWER_ERR_STATE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ncu = g_grid > 0 ? g_grid : t->ncu;
-    const int grid = batch < ncu ? batch : ncu;
+    const int64_t units = (int64_t)batch * t->d.halves;      // what the persistent loop walks: positions, or their halves at 15x15
+    const int grid = units < ncu ? (int)units : ncu;
     for (int b = 0; b < t->blocks; ++b)
         for (int second = 0; second < 2; ++second) {
-            const ConvKernel* k = pick(g_engine, second != 0, g_depth);
+            const ConvKernel* k = pick(t->S, g_engine, second != 0, g_depth);
             if (!k) return AF_TOWER_ERR_ARG;
-            hipLaunchKernelGGL(k->fn, dim3(grid), dim3(256), lds_bytes(k->proj), st, layer_args(t, b, second != 0, x_dev, g_dev, batch));
+            hipLaunchKernelGGL(k->fn, dim3(grid), dim3(256), k->lds, st, layer_args(t, b, second != 0, x_dev, g_dev, batch));
         }
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
@@ -1349,14 +1530,14 @@ int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_pt
     // all or nothing: everything is checked before the first launch
     if (!t || !dev_ptrs || !counts || n != 12 + 6 * t->blocks) return AF_TOWER_ERR_ARG;
     for (int i = 0; i < n; ++i)
-        if (!dev_ptrs[i] || counts[i] != update_count(i, t->blocks)) return AF_TOWER_ERR_ARG;
+        if (!dev_ptrs[i] || counts[i] != update_count(i, t->blocks, t->d)) return AF_TOWER_ERR_ARG;
     if (!all_set(t)) return AF_TOWER_ERR_STATE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int b0 = 0; b0 < t->blocks; b0 += kPackBlocks)
         pack_blocks(t, st, b0, t->blocks - b0 < kPackBlocks ? t->blocks - b0 : kPackBlocks, dev_ptrs + 2 + 6 * b0);
     const float* ends[12] = {dev_ptrs[0], dev_ptrs[1]};
     for (int k = 0; k < 10; ++k) ends[2 + k] = dev_ptrs[2 + 6 * t->blocks + k];
-    pack_ends(t, st, ends, 0, kPackEndsThreads);
+    pack_ends(t, st, ends, 0, t->d.ends_threads);
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
@@ -1364,7 +1545,7 @@ int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_pt
 int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes) {
     if (!t || index < 0 || index >= 4 * t->blocks + kEnds) return AF_TOWER_ERR_ARG;
     if (!t->set[group_of(index, t->blocks)]) return AF_TOWER_ERR_STATE;          // its host setter has not run yet
-    const int64_t bytes = buffer_bytes(index, t->blocks);
+    const int64_t bytes = buffer_bytes(index, t->blocks, t->d);
     if (!host_out) return bytes;
     if (cap_bytes < bytes) return AF_TOWER_ERR_ARG;
     TW_HIP_OK(hipSetDevice(t->device));
@@ -1374,7 +1555,7 @@ int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64
 }
 
 int64_t af_tower_flops_per_position(const af_tower* t) {
-    return (int64_t)2 * t->blocks * (128 * 128 * 9 * 2 + 128 * 128) * kNPIX;
+    return (int64_t)2 * t->blocks * (128 * 128 * 9 * 2 + 128 * 128) * t->d.npix;
 }
 
 }  // extern "C"

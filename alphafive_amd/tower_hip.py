@@ -135,6 +135,15 @@ class HipTower(object):
     def store_nchw(self, B):
         return self._xin[:B].permute(0, 1, 4, 2, 3).reshape(B, self.width, self.S, self.S)
 
+    def scratch_nchw(self, B):
+        """bf16 [B, width, S, S]: what the last convolution that wrote the scratch buffer left there — after forward() on a
+        single-block tower, the block's mid activation g = ELU(conv3x3(h) + b1).  Like load_nchw / store_nchw it reads the C8 layout
+        of include/af_tower_bf16.h, which is the same rule at every board size (15x15 runs its convolutions in half boards, but
+        reads and writes whole planes in this layout)."""
+        S = self.S
+        gin = self.g[:, :, S:S + S * S, :].unflatten(2, (S, S))
+        return gin[:B].permute(0, 1, 4, 2, 3).reshape(B, self.width, S, S)
+
     def stem(self, planes):
         """planes fp32 [B,3,S,S] (contiguous) -> the C8 buffer (af_tower_stem_kernel)."""
         B = planes.shape[0]

@@ -1,16 +1,26 @@
 /*
  * af_tower_bf16.h — C ABI of the hand-written gfx950 bf16 residual tower (libaf_tower.so) used by
  * BASELINE configs[4] (11x11, 8 residual blocks of the reference's block type at
- * constant width 128, bf16, performance-only).  One block is genData/network.py:52-56:
+ * constant width 128, bf16, performance-only), and of the same net on 15x15 boards.  One block is genData/network.py:52-56:
  *     r = conv1x1(h) + b_res ;  g = ELU(conv3x3(h) + b1) ;  h' = ELU(r + conv3x3(g) + b2)
  * evaluated as two launches of one kernel (the projection is 8 extra k-steps of the second one) on
  * v_mfma_f32_32x32x16_bf16, fp32 accumulation, activations stored in bf16 like the PyTorch-ROCm bf16
  * evaluator it replaces (alphafive_amd/network_deep.py).
  *
- * Activation layout ("C8"): bf16 [batch][width/8][PIX][8], PIX = (S+2)*S rounded up to 16 (144 at S = 11): rows
+ * Activation layout ("C8"): bf16 [batch][width/8][PIX][8], PIX = (S+2)*S rounded up to 16 (144 at S = 11, 256 at S = 15): rows
  * are stored back to back with one zero row above and below the board, pixel (y, x) at unit S*(y+1) + x (a unit =
  * the 8 channels of one pixel = 16 bytes).  The kernels never write the two zero rows; the missing left / right
  * neighbours of a row's first / last pixel are handled inside the kernel.  The caller owns the two buffers.
+ *
+ *
+ * Sizes per board side S (C = S*S):            S = 11        S = 15
+ *     PIX (units per channel octet)               144           256
+ *     bytes per position and buffer            36,864        65,536
+ *     vin / pin elements per position      484 / 1936    900 / 3600
+ *     policy outputs                              121           225
+ *     vfc1_w / pfc_w / pfc_b elements   30976 / 234256 / 121   57600 / 810000 / 225
+ * Everything 128-wide (stem, blocks, the heads' 1x1 convolutions) has the same sizes at both.  At S = 15 the convolutions run each
+ * board as two half boards (rows 0..7 and 8..14) inside the library; callers see whole planes in the layout above.
  *
  * Plain pointers, int return codes (0 ok, <0 error), no exceptions; one handle per GPU.
  */
@@ -30,7 +40,8 @@ typedef struct af_tower af_tower;
 #define AF_TOWER_ERR_HIP   (-2)
 #define AF_TOWER_ERR_STATE (-3)   /* forward / device update / debug read before the host setter of the weights it needs has run once */
 
-/* board_size must be 11 and width 128 in this build (4 waves x 32 output channels, 4 pixel tiles). */
+/* board_size must be 11 or 15 and width 128 in this build (4 waves x 32 output channels; 4 pixel tiles per position, or per half board
+ * at 15); anything else is AF_TOWER_ERR_ARG.  One device allocation is made here and none later. */
 int af_tower_create(int32_t board_size, int32_t width, int32_t blocks, int32_t device, af_tower** out);
 void af_tower_destroy(af_tower* t);
 
@@ -81,7 +92,8 @@ int af_tower_dense(af_tower* t, void* stream, const void* vin_dev, const void* p
  *     vconv_w, vconv_b, pconv_w, pconv_b,
  *     vfc1_w, vfc1_b, vfc2_w, vfc2_b, pfc_w, pfc_b
  * with element counts stem_w 9600, every 128-wide bias 128, c1_w / c2_w 147456, res_w 16384, vconv_w / vconv_b 512 / 4,
- * pconv_w / pconv_b 2048 / 16, vfc1_w / vfc1_b 30976 / 64, vfc2_w / vfc2_b 64 / 1, pfc_w / pfc_b 234256 / 121.
+ * pconv_w / pconv_b 2048 / 16, vfc1_w / vfc1_b 4*C*64 / 64, vfc2_w / vfc2_b 64 / 1, pfc_w / pfc_b 16*C*C / C with C = S*S:
+ * 30976, 234256 and 121 at S = 11; 57600, 810000 and 225 at S = 15.
  * All or nothing, checked before the first launch: a null handle, array or entry, a wrong n or a wrong count is
  * AF_TOWER_ERR_ARG; a handle whose stem, heads, dense layers and every block have not each been set once through the host
  * setters is AF_TOWER_ERR_STATE.
@@ -100,7 +112,8 @@ int af_tower_update_device(af_tower* t, void* stream, const float* const* dev_pt
  * copies nothing), AF_TOWER_ERR_ARG past the last index or if cap_bytes is too small, AF_TOWER_ERR_STATE for a buffer whose
  * host setter has not run.  Synchronises the device.  4 * blocks + 12 buffers:
  *   4b + 0..3 = w1, w2, b1, b2 of block b; then stem_w, stem_b, heads_w, heads_b, heads_a, heads_b32, dense_wp, dense_wv,
- *   dense_pb, dense_vb1, dense_vw2, dense_vb2. */
+ *   dense_pb, dense_vb1, dense_vw2, dense_vb2.  dense_wp / dense_wv / dense_pb hold 121 x 4 / 31 x 2 fragment sets of 1 KB and 128 words
+ *   at S = 11, 225 x 8 / 57 x 2 and 256 words at S = 15 (the words behind the last policy output are -1e30). */
 int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes);
 
 /* A/B knobs (process-global): key 0 = B-fragment ring depth (0 = per-kernel default, 8, 12, 16), key 1 = persistent
@@ -108,7 +121,10 @@ int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64
  * "no LDS reads" is the build-time macro AF_TOWER_ABL_NOLDS since r3: a run-time test in the MFMA loop was not free), key 3 = convolution kernels
  * (3 = default: af_tower_conv3 — epilogue under the other tile pair's MFMAs — for a block's first convolution and af_tower_conv for its
  * second; 0 = af_tower_conv for both, bit-identical to 3; 2 = af_tower_conv3 for both), key 4 = the heads' 1x1 convolutions (1 MFMA kernel,
- * 0 VALU kernel).  Anything else — an unknown key, a ring depth other than 0 / 8 / 12 / 16, a negative workgroup count, ablation
+ * 0 VALU kernel).  A 15x15 handle honours keys 0, 1 and 2 (default ring depths 12 for a block's first convolution, 6 for its second) and
+ * accepts every value of keys 3 and 4 without effect: both convolutions of a block run af_tower_conv, because af_tower_conv3 walks whole
+ * positions, and the heads run the MFMA kernel (the VALU kernel is one thread per pixel and half of the channels: 11x11 only).
+ * Anything else — an unknown key, a ring depth other than 0 / 8 / 12 / 16, a negative workgroup count, ablation
  * bits outside 0..7, an engine other than 0 / 2 / 3, a heads kernel other than 0 / 1 — returns AF_TOWER_ERR_ARG and leaves the
  * setting as it was. */
 int af_tower_tune(int32_t key, int32_t value);
