@@ -433,6 +433,10 @@ __device__ float pairwise_sum(const float* a, int n) {   // n <= 256
 
 // ----------------------------------------------------------------------------------------------
 // the tick kernel: one wavefront (= one workgroup) per game
+// Functions in front of it: legal_mask, bb_step, game_rows, load_node_rows, puct_scores.  Expand and backup, the collector,
+// calc_policy, record / step / game over, park and yield, the Dirichlet draw and the choice of the cell are spelled out in the kernel
+// body under their headers: as functions they moved registers to scratch in some instantiation, or (expand and backup) cost the
+// headline instantiation 0.9 % of its launch (profiles/tick_kernel_phases.md).
 // ----------------------------------------------------------------------------------------------
 #ifndef AF_TICK_MIN_WAVES
 #define AF_TICK_MIN_WAVES 4   // 4 one-wave workgroups per SIMD = 16 games per CU in flight (measured 0.075 vs 0.088 ms per tick at 3)
@@ -448,6 +452,103 @@ __device__ unsigned long long g_tick_cycles[8192][13];      // 8..11: inside the
 #define TK_T(var)
 #define TK_ACC(slot, a, b)
 #endif
+
+// utils.py:238 get_legal_actions as a bitboard
+template <int KW>
+__device__ __forceinline__ void legal_mask(const EngineParams& P, const u64 (&m)[KW], const u64 (&t)[KW], u64 (&legal)[KW]) {
+#pragma unroll
+    for (int k = 0; k < KW; ++k) legal[k] = ~(m[k] | t[k]) & P.boardmask[k];
+}
+// utils.py:275 step: place my stone at `cell`, flip perspective (the mover's stone becomes "theirs", the sides swap)
+template <int KW>
+__device__ __forceinline__ void bb_step(u64 (&mine)[KW], u64 (&theirs)[KW], int cell) {
+    u64 nm[KW], nt[KW];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { nm[k] = theirs[k]; nt[k] = mine[k]; }
+    bb_set<KW>(nt, cell);
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { mine[k] = nm[k]; theirs[k] = nt[k]; }
+}
+
+// A game's slices of the transposition store and of its path (wave-uniform pointers)
+struct GameRows {
+    u64* nkeys;
+    int32_t *nsum, *fre, *en;
+    float* ew;
+    double* ew64;
+    float* ep;
+    int32_t* ec;
+    uint32_t* slots;
+    int32_t *pnode, *pcell;
+};
+template <int KW, bool W64>
+__device__ __forceinline__ void game_rows(const EngineParams& P, int g, int NCAP, GameRows& R) {
+    constexpr int CP = 64 * KW;
+    R.nkeys = P.node_key + (size_t)g * NCAP * (2 * KW);
+    R.nsum = P.node_sum + (size_t)g * NCAP;
+    R.fre = P.free_idx + (size_t)g * NCAP;
+    R.en = P.edge_n + (size_t)g * NCAP * CP;
+    // fp64 W rows (pipe path) are a separate instantiation: no live range of the other kind
+    R.ew = P.edge_w + (W64 ? (size_t)0 : (size_t)g * NCAP * CP);
+    R.ew64 = P.edge_w64 + (W64 ? (size_t)g * NCAP * CP : (size_t)0);
+    R.ep = P.edge_p + (size_t)g * NCAP * CP;
+    R.ec = P.edge_c + (size_t)g * NCAP * CP;
+    R.slots = P.hash + (size_t)g * (P.hash_mask + 1);
+    R.pnode = P.path_node + (size_t)g * CP;
+    R.pcell = P.path_cell + (size_t)g * CP;
+}
+
+// The five rows of one node as a select reads them
+template <int KW, bool W64>
+struct NodeRows {
+    typedef typename std::conditional<W64, double, float>::type wrow_t;
+    int32_t sum;
+    int32_t raw[KW], c[KW];
+    wrow_t w[KW];
+    float p[KW];
+};
+// The five-row load of node idx: at the top of a select, or as the prefetch right after the argmax
+template <int KW, bool W64>
+__device__ __forceinline__ void load_node_rows(const GameRows& R, int idx, int lane, NodeRows<KW, W64>& r) {
+    constexpr int CP = 64 * KW;
+    r.sum = R.nsum[idx];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const size_t off = (size_t)idx * CP + lane + 64 * k;
+        r.raw[k] = R.en[off];
+        r.c[k] = R.ec[off];
+        if constexpr (W64) r.w[k] = R.ew64[off]; else r.w[k] = R.ew[off];
+        r.p[k] = R.ep[off];
+    }
+}
+
+// player.py:230-279 select_action_q_and_u, the scores: fp64 Q + U rounded to fp32 per legal cell (sc), and the lane's maximum (mx)
+template <int KW, bool W64>
+__device__ __forceinline__ void puct_scores(const EngineParams& P, int lane, const u64 (&legal)[KW], const int (&nn)[KW], const bool (&ff)[KW],
+                                            const typename NodeRows<KW, W64>::wrow_t (&ww)[KW], const float (&pp)[KW],
+                                            const double (&dd)[KW], bool is_root, int sum_n, float (&sc)[KW], float& mx) {
+    const double sq = sqrt((double)(sum_n + 1));
+    mx = -3.0e38f;
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const bool lg = (legal[k] >> lane) & 1ull;
+        double q64;                                                 // SURVEY §8a rule 2
+        if (nn[k] == 0) q64 = 0.0;
+        else if (!W64 && ff[k]) q64 = (double)((float)ww[k] / (float)nn[k]);
+        else q64 = (double)ww[k] / (double)nn[k];
+        double t;
+        if (P.training) {                                           // rule 3
+            double p_;
+            if (is_root) p_ = (double)(0.75f * pp[k]) + 0.25 * dd[k];
+            else p_ = (double)(0.9f * pp[k]) + 0.1 * dd[k];
+            t = ((P.c_puct * p_) * sq) / (double)(1 + nn[k]);
+        } else {
+            t = ((double)(P.c_puct32 * pp[k]) * sq) / (double)(1 + nn[k]);
+        }
+        sc[k] = lg ? (float)(q64 + t) : -3.0e38f;
+        mx = sc[k] > mx ? sc[k] : mx;
+    }
+}
 
 template <int KW, bool W64, bool MEMO = false>
 __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EngineParams P, const float* __restrict__ policy_in,
@@ -494,32 +595,22 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
     for (int i = 0; i < CT_N; ++i) ct[i] = 0;
     int err = 0;
 
-    u64* const nkeys = P.node_key + (size_t)g * NCAP * (2 * KW);
-    int32_t* const nsum = P.node_sum + (size_t)g * NCAP;
-    int32_t* const fre = P.free_idx + (size_t)g * NCAP;
-    int32_t* const en = P.edge_n + (size_t)g * NCAP * CP;
-    constexpr bool w64 = W64;                        // fp64 W rows (pipe path) are a separate instantiation: no live range of the other kind
-    float* const ew = P.edge_w + (w64 ? (size_t)0 : (size_t)g * NCAP * CP);
-    double* const ew64 = P.edge_w64 + (w64 ? (size_t)g * NCAP * CP : (size_t)0);
-    float* const ep = P.edge_p + (size_t)g * NCAP * CP;
-    int32_t* const ec = P.edge_c + (size_t)g * NCAP * CP;
-    uint32_t* const slots = P.hash + (size_t)g * (P.hash_mask + 1);
-    int32_t* const pnode = P.path_node + (size_t)g * CP;
-    int32_t* const pcell = P.path_cell + (size_t)g * CP;
+    GameRows R;
+    game_rows<KW, W64>(P, g, NCAP, R);
 
     // backup along the stored path: player.py:166-184 update_tree.  Path element d receives
     // v * (-1)^(depth-d); is_f32 marks net values (np.float32) vs terminal values (python float).
     auto backup = [&](int depth, float v, int is_f32) {
         for (int d = lane; d < depth; d += 64) {
-            const size_t off = (size_t)pnode[d] * CP + pcell[d];
+            const size_t off = (size_t)R.pnode[d] * CP + R.pcell[d];
             const float vv = ((depth - d) & 1) ? -v : v;
-            const int32_t raw = en[off];
-            if (w64) {                                      // float(v): every addend is a python float
-                en[off] = raw + 1;
-                ew64[off] = ew64[off] + (double)vv;
+            const int32_t raw = R.en[off];
+            if (W64) {                                      // float(v): every addend is a python float
+                R.en[off] = raw + 1;
+                R.ew64[off] = R.ew64[off] + (double)vv;
             } else {
-                en[off] = (raw + 1) | (is_f32 ? (int32_t)0x80000000 : 0);
-                ew[off] = ew[off] + vv;
+                R.en[off] = (raw + 1) | (is_f32 ? (int32_t)0x80000000 : 0);
+                R.ew[off] = R.ew[off] + vv;
             }
         }
         __syncthreads();
@@ -552,8 +643,7 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
     if (have_eval) {
         have_eval = false;
         u64 legal[KW];
-#pragma unroll
-        for (int k = 0; k < KW; ++k) legal[k] = ~(lm[k] | lt[k]) & P.boardmask[k];
+        legal_mask<KW>(P, lm, lt, legal);
         const int depth = c_depth;
         const uint32_t slot = c_slot;
         float pk[KW];
@@ -580,20 +670,20 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             err = AF_ERR_NODE_CAP;
         } else {
             int idx;
-            if (nfree > 0) idx = rfli(fre[--nfree]); else idx = nodes++;
-            if (lane < 2 * KW) nkeys[(size_t)idx * 2 * KW + lane] = key_word<KW>(lm, lt, lane);
+            if (nfree > 0) idx = rfli(R.fre[--nfree]); else idx = nodes++;
+            if (lane < 2 * KW) R.nkeys[(size_t)idx * 2 * KW + lane] = key_word<KW>(lm, lt, lane);
             if (lane == 0) {
-                nsum[idx] = 0; slots[slot] = (uint32_t)idx + 1u;
+                R.nsum[idx] = 0; R.slots[slot] = (uint32_t)idx + 1u;
                 // child cache of the parent edge (see the descent below): the move that led here now has a node
-                if (depth > 0) ec[(size_t)pnode[depth - 1] * CP + pcell[depth - 1]] = idx + 1;
+                if (depth > 0) R.ec[(size_t)R.pnode[depth - 1] * CP + R.pcell[depth - 1]] = idx + 1;
             }
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
                 const size_t off = (size_t)idx * CP + lane + 64 * k;
-                en[off] = 0;
-                ec[off] = 0;
-                if (w64) ew64[off] = 0.0; else ew[off] = 0.0f;
-                ep[off] = ((legal[k] >> lane) & 1ull) ? pk[k] / s : 0.0f;
+                R.en[off] = 0;
+                R.ec[off] = 0;
+                if (W64) R.ew64[off] = 0.0; else R.ew[off] = 0.0f;
+                R.ep[off] = ((legal[k] >> lane) & 1ull) ? pk[k] / s : 0.0f;
             }
             __syncthreads();
             backup(depth, rflf(*c_val), 1);
@@ -628,7 +718,7 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             // game's free stack (reused by later expands) and the hash is rebuilt from the survivors.
             bool collected = false;
             if (nodes - nfree + P.sims + 2 > NCAP && nodes > 0) {
-                for (uint32_t s_ = lane; s_ <= P.hash_mask; s_ += 64) slots[s_] = 0;
+                for (uint32_t s_ = lane; s_ <= P.hash_mask; s_ += 64) R.slots[s_] = 0;
                 __syncthreads();
                 const int rc = bb_count<KW>(root_m) + bb_count<KW>(root_t);
                 int nf = 0;
@@ -636,10 +726,10 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                     const int i = base + lane;
                     const bool valid = i < nodes;
                     bool keep = false;
-                    if (valid && nsum[i] >= 0) {
+                    if (valid && R.nsum[i] >= 0) {
                         u64 nm[KW], nt[KW];
 #pragma unroll
-                        for (int k = 0; k < KW; ++k) { nm[k] = nkeys[(size_t)i * 2 * KW + k]; nt[k] = nkeys[(size_t)i * 2 * KW + KW + k]; }
+                        for (int k = 0; k < KW; ++k) { nm[k] = R.nkeys[(size_t)i * 2 * KW + k]; nt[k] = R.nkeys[(size_t)i * 2 * KW + KW + k]; }
                         const int nc = bb_count<KW>(nm) + bb_count<KW>(nt);
                         keep = true;
                         // colour of "mine" is fixed by stone-count parity
@@ -653,15 +743,15 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                             uint32_t h = key_hash<KW>(nm, nt);
                             for (;;) {
                                 h &= P.hash_mask;
-                                if (atomicCAS(&slots[h], 0u, (uint32_t)i + 1u) == 0u) break;
+                                if (atomicCAS(&R.slots[h], 0u, (uint32_t)i + 1u) == 0u) break;
                                 ++h;
                             }
                         } else {
-                            nsum[i] = -1;
+                            R.nsum[i] = -1;
                         }
                     }
                     const u64 dm = __ballot(valid && !keep);
-                    if (valid && !keep) fre[nf + __popcll(dm & ((1ull << lane) - 1ull))] = i;
+                    if (valid && !keep) R.fre[nf + __popcll(dm & ((1ull << lane) - 1ull))] = i;
                     nf += __popcll(dm);
                 }
                 nfree = nf;
@@ -673,7 +763,7 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             uint32_t slot;
             const int ridx = tree_lookup<KW>(P, g, root_m, root_t, lane, &slot);
             int num = P.sims;                                           // player.py:140-143
-            if (ridx >= 0) { const int rem = P.upper - rfli(nsum[ridx]); num = rem < num ? rem : num; }
+            if (ridx >= 0) { const int rem = P.upper - rfli(R.nsum[ridx]); num = rem < num ? rem : num; }
             sims_left = num;
             phase = PH_SEARCH;
             // the collector is this launch's work: search resumes at the next tick
@@ -686,15 +776,14 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             const int ridx = tree_lookup<KW>(P, g, root_m, root_t, lane, &slot);
             if (ridx < 0) { err = AF_ERR_NO_ROOT; break; }
             u64 legal[KW];
-#pragma unroll
-            for (int k = 0; k < KW; ++k) legal[k] = ~(root_m[k] | root_t[k]) & P.boardmask[k];
+            legal_mask<KW>(P, root_m, root_t, legal);
             const int L = bb_count<KW>(legal);
             int nv[KW];
             int most = -1;
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
                 const bool lg = (legal[k] >> lane) & 1ull;
-                nv[k] = lg ? (en[(size_t)ridx * CP + lane + 64 * k] & 0x7fffffff) : -1;
+                nv[k] = lg ? (R.en[(size_t)ridx * CP + lane + 64 * k] & 0x7fffffff) : -1;
                 most = nv[k] > most ? nv[k] : most;
             }
             most = wave_max_i32(most);
@@ -789,20 +878,14 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                 if (c < C) { P.rec_policy[rslot * C + c] = pol[k]; P.rec_visits[rslot * C + c] = nv[k] < 0 ? 0 : nv[k]; }
             }
             if (lane == 0) { P.rec_last[rslot] = root_last; P.rec_action[rslot] = action; }
-            // utils.py:275 step: place my stone, flip perspective
-            {
-                u64 nm[KW], nt[KW];
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { nm[k] = root_t[k]; nt[k] = root_m[k]; }
-                bb_set<KW>(nt, action);
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { root_m[k] = nm[k]; root_t[k] = nt[k]; }
-            }
+            bb_step<KW>(root_m, root_t, action);
             root_last = action;
             ++ply;
             float fv;
             if (terminal_test<KW>(P, root_m, root_t, &fv)) {
-                // episode finished: publish, then Player.reset() (:73) and start the next game
+                // episode finished: publish, then Player.reset() (:73) and start the next game.  The reset is install_root's
+                // sequence on this launch's registers, not a call of it: the game's state lives in registers until "3. store
+                // state", which would overwrite whatever install_root wrote to memory
                 if (seq - rfl32(P.ep_popped[g]) >= 2u) { err = AF_ERR_EP_OVERRUN; break; }
                 if (lane == 0) {
                     P.ep_len[(size_t)g * 2 + (seq & 1u)] = ply;
@@ -811,7 +894,7 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                 }
                 ct[CT_EPISODES]++;
                 if (lane == 0) atomicAdd(&P.progress[1], 1ull);
-                for (uint32_t s_ = lane; s_ <= P.hash_mask; s_ += 64) slots[s_] = 0;
+                for (uint32_t s_ = lane; s_ <= P.hash_mask; s_ += 64) R.slots[s_] = 0;
                 __syncthreads();
                 nodes = 0; nfree = 0;
 #pragma unroll
@@ -851,11 +934,9 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
         int hint = 0, pidx = -1, pcl = 0;
         // ... and the child's rows are requested as soon as its index is known (right after the argmax), so that they travel
         // while the move is played and the terminal test runs
-        typedef typename std::conditional<W64, double, float>::type wrow_t;
-        int32_t r_raw[KW], r_c[KW];
-        float r_p[KW];
-        wrow_t r_w[KW];
-        int32_t r_sum = 0;
+        typedef typename NodeRows<KW, W64>::wrow_t wrow_t;
+        NodeRows<KW, W64> r;
+        r.sum = 0;
         bool r_have = false;
         for (;;) {
             TK_T(tk_a);
@@ -883,7 +964,7 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                 idx = hint - 1;
             } else {
                 idx = tree_lookup<KW>(P, g, cm, ctb, lane, &slot);
-                if (idx >= 0 && pidx >= 0 && lane == 0) ec[(size_t)pidx * CP + pcl] = idx + 1;   // reached through another move order before
+                if (idx >= 0 && pidx >= 0 && lane == 0) R.ec[(size_t)pidx * CP + pcl] = idx + 1;   // reached through another move order before
             }
             if (idx < 0) {                                                  // :218 unseen -> park for the net
                 if constexpr (MEMO) {
@@ -933,23 +1014,15 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             TK_ACC(3, tk_a, tk_b);
             // ------------- player.py:230-279 select_action_q_and_u -------------
             const bool is_root = depth == 0;
+            // (legal_mask spelled out: with no loop over a field of P left in the kernel body itself, hipcc reads every field of P
+            // once at the top of the kernel and keeps it in registers — more scratch in five of the eight instantiations)
             u64 legal[KW];
 #pragma unroll
             for (int k = 0; k < KW; ++k) legal[k] = ~(cm[k] | ctb[k]) & P.boardmask[k];
-            if (!r_have) {
-                r_sum = nsum[idx];
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    const size_t off = (size_t)idx * CP + lane + 64 * k;
-                    r_raw[k] = en[off];
-                    r_c[k] = ec[off];
-                    if constexpr (W64) r_w[k] = ew64[off]; else r_w[k] = ew[off];
-                    r_p[k] = ep[off];
-                }
-            }
+            if (!r_have) load_node_rows<KW, W64>(R, idx, lane, r);
             r_have = false;
-            const int sum_n = rfli(r_sum) + 1;                              // :237
-            if (lane == 0) nsum[idx] = sum_n;
+            const int sum_n = rfli(r.sum) + 1;                              // :237
+            if (lane == 0) R.nsum[idx] = sum_n;
             const uint32_t sel_id = sel++;
             int nn[KW];
             float pp[KW];
@@ -958,11 +1031,11 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             int32_t cc[KW];
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
-                nn[k] = r_raw[k] & 0x7fffffff;
-                ff[k] = r_raw[k] < 0;
-                cc[k] = r_c[k];
-                ww[k] = r_w[k];
-                pp[k] = r_p[k];
+                nn[k] = r.raw[k] & 0x7fffffff;
+                ff[k] = r.raw[k] < 0;
+                cc[k] = r.c[k];
+                ww[k] = r.w[k];
+                pp[k] = r.p[k];
             }
             double dd[KW];
             if (P.training) {
@@ -1057,28 +1130,8 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
                 TK_ACC(9, tk_n1, tk_n1e);
             }
             TK_T(tk_n2);
-            const double sq = sqrt((double)(sum_n + 1));
-            float sc[KW];
-            float mx = -3.0e38f;
-#pragma unroll
-            for (int k = 0; k < KW; ++k) {
-                const bool lg = (legal[k] >> lane) & 1ull;
-                double q64;                                                 // SURVEY §8a rule 2
-                if (nn[k] == 0) q64 = 0.0;
-                else if (!W64 && ff[k]) q64 = (double)((float)ww[k] / (float)nn[k]);
-                else q64 = (double)ww[k] / (double)nn[k];
-                double t;
-                if (P.training) {                                           // rule 3
-                    double p_;
-                    if (is_root) p_ = (double)(0.75f * pp[k]) + 0.25 * dd[k];
-                    else p_ = (double)(0.9f * pp[k]) + 0.1 * dd[k];
-                    t = ((P.c_puct * p_) * sq) / (double)(1 + nn[k]);
-                } else {
-                    t = ((double)(P.c_puct32 * pp[k]) * sq) / (double)(1 + nn[k]);
-                }
-                sc[k] = lg ? (float)(q64 + t) : -3.0e38f;
-                mx = sc[k] > mx ? sc[k] : mx;
-            }
+            float sc[KW], mx;
+            puct_scores<KW, W64>(P, lane, legal, nn, ff, ww, pp, dd, is_root, sum_n, sc, mx);
             TK_T(tk_n3);
             TK_ACC(10, tk_n2, tk_n3);
             int cell = -1;
@@ -1109,32 +1162,15 @@ __global__ __launch_bounds__(64, AF_TICK_MIN_WAVES) void af_tick_kernel(EnginePa
             hint = rfli(hint);
             pidx = idx; pcl = cell;
             if (hint) {
-                const int ci = hint - 1;
-                r_sum = nsum[ci];
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    const size_t off = (size_t)ci * CP + lane + 64 * k;
-                    r_raw[k] = en[off];
-                    r_c[k] = ec[off];
-                    if constexpr (W64) r_w[k] = ew64[off]; else r_w[k] = ew[off];
-                    r_p[k] = ep[off];
-                }
+                load_node_rows<KW, W64>(R, hint - 1, lane, r);
                 r_have = true;
             }
             ++work;
             ct[CT_SELECTS]++;
             ct[CT_LSUM] += (uint32_t)bb_count<KW>(legal);
-            if (lane == 0) { pnode[depth] = idx; pcell[depth] = cell; }
+            if (lane == 0) { R.pnode[depth] = idx; R.pcell[depth] = cell; }
             ++depth;
-            // utils.py:275 step
-            {
-                u64 nm[KW], nt[KW];
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { nm[k] = ctb[k]; nt[k] = cm[k]; }
-                bb_set<KW>(nt, cell);
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { cm[k] = nm[k]; ctb[k] = nt[k]; }
-            }
+            bb_step<KW>(cm, ctb, cell);
             last = cell;
             __syncthreads();
             TK_T(tk_c);
@@ -1294,7 +1330,8 @@ __global__ __launch_bounds__(256) void af_pack_copy(EngineParams P, int max_eps,
 // games with one upload, one launch and one download instead of a device synchronisation and ~10 tiny copies per game
 // ----------------------------------------------------------------------------------------------
 // Player.get_action(state, last, random_a) for game g, by the wave that owns the request: `word` = key word `lane` of the new root
-// (read by the lanes below KW2 only).  The one place that knows the reset sequence; af_set_roots_kernel and af_match_step_kernel call it.
+// (read by the lanes below KW2 only).  The one place that knows the reset sequence on a game's state in memory; af_set_roots_kernel
+// and af_match_step_kernel call it.  (af_tick_kernel's episode end restates it on the registers it holds that state in for the launch.)
 __device__ __forceinline__ void install_root(const EngineParams& P, int g, int lane, int KW2, u64 word, int last, int ra, int reset) {
     if (reset) {                                                 // Player.reset(): player.py:48-51
         uint32_t* slots = P.hash + (size_t)g * (P.hash_mask + 1);
@@ -1400,13 +1437,9 @@ __device__ __forceinline__ void match_step_game(const EngineParams& P, const Eng
         }
         return;
     }
-    // utils.py:275 step: the mover's stone becomes "theirs", the sides swap
-    u64 nm[KW], nt[KW];
-#pragma unroll
-    for (int k = 0; k < KW; ++k) { nm[k] = rt[k]; nt[k] = rm[k]; }
-    bb_set<KW>(nt, action);
+    bb_step<KW>(rm, rt, action);
     float fv;
-    const int over = terminal_test<KW>(P, nm, nt, &fv);
+    const int over = terminal_test<KW>(P, rm, rt, &fv);
     const int nply = ply + 1;
     if (lane == 0) {
         M.moves[(size_t)g * P.C + ply] = action;
@@ -1423,7 +1456,7 @@ __device__ __forceinline__ void match_step_game(const EngineParams& P, const Eng
     }
     if (over || nply >= max_plies) return;
     // the opponent's get_action(state, last_action = action, random_a = True); Player.reset() before its first move of the game
-    install_root(Q, g, lane, 2 * KW, key_word<KW>(nm, nt, lane), action, 1, nply < 2 ? 1 : 0);
+    install_root(Q, g, lane, 2 * KW, key_word<KW>(rm, rt, lane), action, 1, nply < 2 ? 1 : 0);
 }
 
 template <int KW>

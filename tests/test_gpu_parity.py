@@ -167,6 +167,47 @@ def test_selfplay_engine_value_f64_matches_pipe_oracle_run():
     sp.close()
 
 
+def test_selfplay_engine_value_f64_four_word_boards_match_pipe_oracle_run():
+    """The same on a 12x12 board (144 cells: four-word bitboards with fp64 W rows), without and with the evaluation memo: the first
+    episode of every game is the oracle's, and the memo (4 games are enough for hits) changes no episode."""
+    from alphafive_amd import engine as eng
+    from alphafive_amd.engine import SelfPlayEngine
+    cfg = make_cfg(board_size=12, goal=4, simulation_per_step=24, upper_simulation_per_step=30)
+    G = 4
+    pv = lambda x: pseudonet.pseudonet_torch(x, 31, 8192, 24)
+
+    def first_episodes(**kw):
+        sp = SelfPlayEngine(cfg, G, pv, device=0, seed=12, value_f64=True, **kw)
+        assert sp.engine.KW2 == 8 == eng.key_words(12)
+        eps = {}
+        for _ in range(400):
+            sp.run_ticks(64)
+            sp.check()
+            for raw in sp.pop_raw(cap=64):
+                eps.setdefault(raw["game"], raw)
+            if len(eps) == G:
+                break
+        assert len(eps) == G
+        hits = sp.engine.memo_stats()["hits"] if "eval_memo" in kw else 0
+        sp.close()
+        return eps, hits
+
+    eps, _ = first_episodes()
+    for g in range(G):
+        orc = oracle.OraclePlayer(cfg, training=True, rng_mode=oracle.RNG_PHILOX, seed=12, game_id=g, value_f64=True,
+                                  pv_fn=lambda x: pseudonet.pseudonet_np(x, 31, 8192, 24))
+        orec, extra = orc.run()
+        raw = eps[g]
+        assert raw["seq"] == 0 and raw["T"] == len(orec)
+        assert (raw["actions"] == extra["actions"]).all() and (raw["visits"] == extra["visits"]).all()
+        assert raw["final_value"] == extra["final_value"]
+    meps, hits = first_episodes(eval_memo=dict(log2_buckets=8, max_stones=6), weights_version=0)
+    assert hits > 0
+    for g in range(G):
+        assert meps[g]["seq"] == 0 and meps[g]["T"] == eps[g]["T"] and meps[g]["final_value"] == eps[g]["final_value"]
+        assert (meps[g]["actions"] == eps[g]["actions"]).all() and (meps[g]["visits"] == eps[g]["visits"]).all()
+
+
 def test_player_run_and_reset_match_oracle():
     from alphafive_amd.player import Player
     cfg = make_cfg(board_size=6, goal=4, simulation_per_step=60, upper_simulation_per_step=80)

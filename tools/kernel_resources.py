@@ -3,7 +3,7 @@
     hipcc ... -Rpass-analysis=kernel-resource-usage -o /dev/null x.hip 2> remarks.txt
     python tools/kernel_resources.py remarks.txt [other.txt]
 
-One file: a markdown table (kernel, VGPRs, AGPRs, scratch bytes per lane, static LDS bytes, occupancy).  Two files: the kernels of
+One file: a markdown table (kernel, VGPRs, AGPRs, scratch bytes per lane, static LDS bytes, occupancy, VGPR and SGPR spills).  Two files: the kernels of
 the first whose demangled name, with every `Geo<11>, ` template argument dropped, is also in the second, side by side — how a
 build before and after a change that only added template parameters is compared; exit status 1 if any figure differs."""
 import re
@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 FIELDS = (("VGPRs", "VGPRs"), ("AGPRs", "AGPRs"), ("ScratchSize [bytes/lane]", "scratch"), ("LDS Size [bytes/block]", "LDS"),
-          ("Occupancy [waves/SIMD]", "occupancy"))
+          ("Occupancy [waves/SIMD]", "occupancy"), ("VGPRs Spill", "VGPR spills"), ("SGPRs Spill", "SGPR spills"))
 
 
 def parse(path):
