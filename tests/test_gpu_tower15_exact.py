@@ -1,19 +1,22 @@
 """The bf16 tower kernels on 15x15 boards (csrc/af_tower_bf16.hip, Geo<15>) against oracle/tower_fp64.py, one layer at a time.
-The cases, the two regimes and the error bound are those of tests/test_tower15_reference_cpu.py, which also proves — without a
-GPU — that the exact-regime cases meet the conditions under which the kernels must reproduce fp64 bit for bit.
+The cases, the two regimes and the error bound are those of tests/tower_cases.py; tests/test_tower15_reference_cpu.py proves —
+without a GPU — that the exact-regime cases meet the conditions under which the kernels must reproduce fp64 bit for bit.
 
 What is particular to 15x15: the convolution runs every board as two half-board pseudo-positions (rows 0..7 and 8..14) that stage
 one row of their sibling; the block's second convolution runs in place, so a half may stage a row its sibling has already
 overwritten.  It must never multiply it: the "conv2" and "proj" isolations, whose outputs on rows 7 and 8 depend on stones on both
 sides of the seam, are wrong integers if it does.  Stem, heads and dense layers run whole positions in 8 tiles."""
-import numpy as np
 import pytest
 
-import test_tower15_reference_cpu as gen
+import tower_cases as gen
+import tower_gpu
 from oracle import tower_fp64 as ref64
+from tower_cases import ISOLATIONS, NDIST, W
+from tower_gpu import _assert_untouched, _mismatch, _null_block, _poison, _run_block, _t, _tower, _Tune, _worst_ratio
 
-S, W, NPIX, NPOS, NDIST, NROUND = gen.S, gen.W, gen.NPIX, gen.NPOS, gen.NDIST, gen.NROUND
-ISOLATIONS = gen.ISOLATIONS
+pytestmark = pytest.mark.gpu
+S = 15
+NPIX, NROUND = gen.SIZES[S].NPIX, gen.SIZES[S].NROUND
 DEPTHS = (0, 8, 12, 16)          # tune key 0: the default ring depths (12 / 6), then each depth the key accepts
 # (batch, persistent workgroups = tune key 1; 0 = one per CU, at most one per half board)
 #   1, 2, 3: a single position, two, an odd count (6 half boards)
@@ -23,100 +26,6 @@ DEPTHS = (0, 8, 12, 16)          # tune key 0: the default ring depths (12 / 6),
 #   130: 260 half boards, more than one pass of 256 workgroups;  232: every (cin, pixel) site non-zero once
 CONFIGS = ((1, 0), (2, 0), (3, 0), (9, 8), (17, 8), (25, 8), (130, 0), (232, 0))
 
-pytestmark = pytest.mark.gpu
-SENT16 = 0x4B4B                  # bf16 bit pattern (a finite 1.3e7) no kernel here can produce
-SENT32 = -777.25
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to("cuda", dtype or torch.float32)
-
-
-def _null_block():
-    import torch
-    z3, z1, zb = torch.zeros(W, W, 3, 3), torch.zeros(W, W, 1, 1), torch.zeros(W)
-    return dict(c1=(z3, zb), c2=(z3, zb), res=(z1, zb))
-
-
-def _tower(case, max_batch, **kw):
-    import torch
-    from alphafive_amd import tower_hip
-    tt = lambda wb: (torch.from_numpy(np.asarray(wb[0], np.float32)), torch.from_numpy(np.asarray(wb[1], np.float32)))  # noqa: E731
-    blocks = [dict(c1=tt(case["c1"]), c2=tt(case["c2"]), res=tt(case["res"]))] if "c1" in case else [_null_block()]
-    for k in ("stem", "vconv", "pconv"):
-        if k in kw:
-            kw[k] = tt(kw[k])
-    if "dense" in kw:
-        kw["dense"] = tuple(torch.from_numpy(np.asarray(a, np.float32)) for a in kw["dense"])
-    return tower_hip.HipTower(blocks, S, W, max_batch, "cuda:0", **kw)
-
-
-def _bits16(t):
-    import torch
-    return t.view(torch.int16)
-
-
-def _poison(tw, B):
-    """Positions at or past B of every buffer a kernel writes hold a sentinel; the zero rows of the positions below B are zero."""
-    for buf in (tw.x, tw.g, tw.vin, tw.pin):
-        _bits16(buf[B:]).fill_(SENT16)
-    for buf in (tw.x, tw.g):
-        buf[:B, :, :S] = 0
-        buf[:B, :, S + NPIX:] = 0
-    tw.policy[B:].fill_(SENT32)
-    tw.value[B:].fill_(SENT32)
-
-
-def _assert_untouched(tw, B):
-    """... and still do, bit for bit; the two zero rows (and the pad unit behind them) of the positions below B are still zero."""
-    import torch
-    torch.cuda.synchronize()
-    for name in ("x", "g", "vin", "pin"):
-        assert bool((_bits16(getattr(tw, name)[B:]) == SENT16).all()), f"{name}: a position at or past batch {B} was written"
-    for name in ("policy", "value"):
-        assert bool((getattr(tw, name)[B:] == SENT32).all()), f"{name}: a position at or past batch {B} was written"
-    for name in ("x", "g"):
-        buf = getattr(tw, name)[:B]
-        assert not bool(_bits16(buf[:, :, :S]).any()) and not bool(_bits16(buf[:, :, S + NPIX:]).any()), f"{name}: a zero row was written"
-
-
-class _Tune(object):
-    """Tune keys set for one run; every key is put back to its default whatever happens."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        from alphafive_amd import tower_hip
-        try:
-            for k, v in self.kv.items():
-                tower_hip.tune(int(k[1:]), v)
-        except Exception:
-            self.__exit__()
-            raise
-
-    def __exit__(self, *exc):
-        from alphafive_amd import tower_hip
-        for k, v in ((0, 0), (1, 0), (2, 0), (3, 3), (4, 1)):
-            tower_hip.tune(k, v)
-
-
-def _run_block(tw, h_dev, B, depth, grid, engine=3):
-    _poison(tw, B)
-    tw.load_nchw(h_dev[:B])
-    with _Tune(k3=engine, k0=depth, k1=grid):
-        tw.forward(B)
-    _assert_untouched(tw, B)
-    return tw.store_nchw(B), tw.scratch_nchw(B)
-
-
-def _mismatch(out, ref):
-    bad = (out != ref).nonzero()
-    return "%d of %d elements differ; first at (position, channel, y, x) = %s: got %s, expected %s; rows hit: %s" % (
-        bad.shape[0], out.numel(), bad[0].tolist(), out[tuple(bad[0])].item(), ref[tuple(bad[0])].item(),
-        sorted(set(bad[:, 2].tolist()))) if bad.shape[0] else "equal"
-
 
 def test_the_library_takes_11_and_15_and_nothing_else():
     from alphafive_amd import tower_hip
@@ -124,7 +33,7 @@ def test_the_library_takes_11_and_15_and_nothing_else():
         with pytest.raises(tower_hip.TowerError) as e:
             tower_hip.HipTower([_null_block()], size, W, 1, "cuda:0")
         assert e.value.code == -1
-    tw = _tower({}, 2)
+    tw = _tower(S, {}, 2)
     try:
         assert tw.pix == 256 and tw.x.shape == (2, 16, 256, 8) and tw.policy.shape == (2, 225)
         assert tw.flops_per_position == 2 * (128 * 128 * 19) * 225
@@ -134,36 +43,14 @@ def test_the_library_takes_11_and_15_and_nothing_else():
 
 @pytest.fixture(scope="module")
 def block_towers():
-    """One single-block tower per isolation and regime, with its input on the device and — exact regime — the reference."""
-    import torch
-    made = {}
-
-    def get(regime, iso):
-        if (regime, iso) not in made:
-            case = gen.exact_block_case(iso) if regime == "exact" else gen.rounded_block_case(iso)
-            n = case["h"].shape[0]
-            tw = _tower(case, n + 8)
-            ref = None
-            if regime == "exact":
-                g, _, out, _ = gen.exact_block_reference(iso)
-                ref = (_t(ref64.bf16_round(out), torch.bfloat16), _t(ref64.bf16_round(g), torch.bfloat16))
-            made[(regime, iso)] = (tw, _t(case["h"], torch.bfloat16), ref)
-        return made[(regime, iso)]
-    yield get
-    for tw, _, _ in made.values():
-        tw.close()
+    yield from tower_gpu.block_towers(S)
 
 
 @pytest.mark.parametrize("depth", DEPTHS)
 @pytest.mark.parametrize("iso", ISOLATIONS)
 def test_block_convolutions_are_exact(block_towers, iso, depth):
     """Every (cout, cin, tap, pixel, position) of one convolution, at every ring depth, batch and grid: bit equality with fp64."""
-    import torch
-    tw, h_dev, (ref_out, ref_g) = block_towers("exact", iso)
-    for B, grid in CONFIGS:
-        out, g = _run_block(tw, h_dev, B, depth, grid)
-        assert torch.equal(g, ref_g[:B]), f"mid activation, batch {B}, grid {grid}: " + _mismatch(g, ref_g[:B])
-        assert torch.equal(out, ref_out[:B]), f"block output, batch {B}, grid {grid}: " + _mismatch(out, ref_out[:B])
+    tower_gpu.check_block_convolutions_are_exact(block_towers, iso, depth, CONFIGS)
 
 
 @pytest.mark.parametrize("engine", [0, 2])
@@ -177,18 +64,14 @@ def test_tune_key_3_changes_nothing_on_a_15x15_handle(block_towers, engine):
 
 @pytest.fixture(scope="module")
 def ends_tower():
-    """Stem + heads of the exact regime on one tower (null block)."""
-    st, hd = gen.exact_stem_case(), gen.exact_heads_case()
-    tw = _tower({}, NDIST + 5 + 3, stem=(st["w"], st["b"]), vconv=hd["vconv"], pconv=hd["pconv"])
-    yield tw
-    tw.close()
+    yield from tower_gpu.ends_tower(S, NDIST + 5 + 3)
 
 
 @pytest.mark.parametrize("B", [1, 3, NDIST + 5])
 def test_stem_is_exact(ends_tower, B):
     """All 75 taps at corners, edges, the interior and both sides of the seam; a full, an empty and randomly filled boards."""
     import torch
-    tw, case = ends_tower, gen.exact_stem_case()
+    tw, case = ends_tower, gen.exact_stem_case(S)
     y, _ = ref64.stem(case["planes"], case["w"], case["b"])
     ref = _t(ref64.bf16_round(y), torch.bfloat16)
     # batches 1 and 3 would see only the full and the empty board and one single stone: rotate so that each batch starts elsewhere
@@ -204,7 +87,7 @@ def test_stem_is_exact(ends_tower, B):
 def test_stem_single_stones_and_boards_one_position_at_a_time(ends_tower):
     """Batch 1 on each of the 64 distinct positions: the full board, the empty one, every single stone, the random fills."""
     import torch
-    tw, case = ends_tower, gen.exact_stem_case()
+    tw, case = ends_tower, gen.exact_stem_case(S)
     y, _ = ref64.stem(case["planes"], case["w"], case["b"])
     ref = _t(ref64.bf16_round(y), torch.bfloat16)
     planes = _t(case["planes"])
@@ -220,7 +103,7 @@ def test_stem_single_stones_and_boards_one_position_at_a_time(ends_tower):
 def test_heads_are_exact(ends_tower, B):
     """The heads' 1x1 convolutions on an integer tower output: the MFMA kernel (the only one at 15x15, whatever key 4 says) = fp64."""
     import torch
-    tw, case = ends_tower, gen.exact_heads_case()
+    tw, case = ends_tower, gen.exact_heads_case(S)
     vin, _, pin, _ = ref64.heads(case["h"], case["vconv"], case["pconv"])
     ref_v, ref_p = _t(ref64.bf16_round(vin), torch.bfloat16), _t(ref64.bf16_round(pin), torch.bfloat16)
     idx = torch.arange(B, device="cuda") % NDIST
@@ -238,44 +121,17 @@ def test_heads_are_exact(ends_tower, B):
 
 @pytest.fixture(scope="module")
 def dense_tower():
-    c = gen.exact_dense_case()
-    tw = _tower({}, 65 + 3, dense=(c["vfc1"][0], c["vfc1"][1], c["vfc2"][0], c["vfc2"][1], c["pfc"][0], c["pfc"][1]))
-    yield tw
-    tw.close()
+    yield from tower_gpu.dense_tower(S, 65 + 3)
 
 
 @pytest.mark.parametrize("B", [1, 31, 32, 33, 65])
 def test_dense_matches_fp64_to_1e5(dense_tower, B):
     """Logits and z are exact in fp32 whatever the summation order, so what is left is __expf, tanhf and one division:
     policy and value within 1e-5 of fp64, every row 225 entries summing to 1 within 1e-5, nothing written past the batch."""
-    import torch
-    tw, c = dense_tower, gen.exact_dense_case()
-    policy, value, _, _ = ref64.dense(c["vin"], c["pin"], c["vfc1"], c["vfc2"], c["pfc"])
-    idx = torch.arange(B, device="cuda") % NDIST
-    _poison(tw, B)
-    tw.vin[:B] = _t(c["vin"], torch.bfloat16)[idx]
-    tw.pin[:B] = _t(c["pin"], torch.bfloat16)[idx]
-    p, v = tw.dense(B)
-    _assert_untouched(tw, B)
-    assert p.shape == (B, NPIX)
-    n = min(B, NDIST)
-    ep = np.abs(p[:n].double().cpu().numpy() - policy[:n]).max()
-    ev = np.abs(v[:n].double().cpu().numpy() - value[:n]).max()
-    es = float((p.double().sum(1) - 1).abs().max())
-    print("dense 15x15 B=%d: max |policy - fp64| %.3g, |value - fp64| %.3g, |row sum - 1| %.3g" % (B, ep, ev, es))
-    assert ep <= 1e-5 and ev <= 1e-5 and es <= 1e-5
-    assert torch.equal(p, p[idx]) and torch.equal(v, v[idx]), "a repeat of a position differs from its first occurrence"
+    tower_gpu.check_dense_matches_fp64_to_1e5(dense_tower, B)
 
 
 # ------------------------------------------------------------------ rounded regime ------------------------------------------------------------------
-def _worst_ratio(out, ref, A, n, what):
-    """max over elements of |out - ref| / bound, printed (the headroom of the derived bound) and returned."""
-    err = np.abs(out.double().cpu().numpy() - ref)
-    ratio = float((err / gen.error_bound(ref, A, n)).max())
-    print("rounded regime 15x15, %s: worst |error| / bound = %.3f (max |error| %.3g)" % (what, ratio, err.max()))
-    return ratio
-
-
 @pytest.mark.parametrize("B", [33, NROUND])
 @pytest.mark.parametrize("iso", ISOLATIONS)
 def test_block_convolutions_meet_the_rounding_bound(block_towers, iso, B):
@@ -283,7 +139,7 @@ def test_block_convolutions_meet_the_rounding_bound(block_towers, iso, B):
     second convolution of the mid activation that was stored, so each comparison crosses exactly one rounding to bf16."""
     import torch
     tw, h_dev, _ = block_towers("rounded", iso)
-    case = gen.rounded_block_case(iso)
+    case = gen.rounded_block_case(S, iso)
     got = {}
     for depth in DEPTHS:
         out, g = _run_block(tw, h_dev, B, depth, 0)
@@ -294,28 +150,28 @@ def test_block_convolutions_meet_the_rounding_bound(block_towers, iso, B):
     assert torch.isfinite(out.float()).all()
     g_ref, A1, out_ref, A2 = ref64.block(case["h"][:B], case["c1"], case["c2"], case["res"], mid=g.double().cpu().numpy())
     assert (g_ref < 0).any() and (out_ref < 0).any()                 # the ELU's negative side is exercised
-    assert _worst_ratio(g, g_ref, A1, 1152, f"{iso} B={B} first convolution") <= 1.0
-    assert _worst_ratio(out, out_ref, A2, 1280, f"{iso} B={B} second convolution + projection") <= 1.0
+    assert _worst_ratio(S, g, g_ref, A1, 1152, f"{iso} B={B} first convolution") <= 1.0
+    assert _worst_ratio(S, out, out_ref, A2, 1280, f"{iso} B={B} second convolution + projection") <= 1.0
 
 
 @pytest.mark.parametrize("B", [33, NROUND])
 def test_stem_and_heads_meet_the_rounding_bound(B):
     import torch
-    c = gen.rounded_ends_case()
-    tw = _tower({}, B + 3, stem=c["stem"], vconv=c["vconv"], pconv=c["pconv"])
+    c = gen.rounded_ends_case(S)
+    tw = _tower(S, {}, B + 3, stem=c["stem"], vconv=c["vconv"], pconv=c["pconv"])
     try:
         y, A = ref64.stem(c["planes"][:B], *c["stem"])
         _poison(tw, B)
         tw.stem(_t(c["planes"][:B]))
         _assert_untouched(tw, B)
         assert (y < 0).any()
-        assert _worst_ratio(tw.store_nchw(B), y, A, 75, f"stem B={B}") <= 1.0
+        assert _worst_ratio(S, tw.store_nchw(B), y, A, 75, f"stem B={B}") <= 1.0
         vin, Av, pin, Ap = ref64.heads(c["h"][:B], c["vconv"], c["pconv"])
         _poison(tw, B)
         tw.load_nchw(_t(c["h"][:B], torch.bfloat16))
         v, p = tw.heads(B)
         _assert_untouched(tw, B)
-        assert _worst_ratio(v, vin, Av, 128, f"heads value B={B}") <= 1.0
-        assert _worst_ratio(p, pin, Ap, 128, f"heads policy B={B}") <= 1.0
+        assert _worst_ratio(S, v, vin, Av, 128, f"heads value B={B}") <= 1.0
+        assert _worst_ratio(S, p, pin, Ap, 128, f"heads policy B={B}") <= 1.0
     finally:
         tw.close()

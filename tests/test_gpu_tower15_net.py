@@ -1,23 +1,17 @@
 """DeepResNet(15) on the hand-written bf16 tower (csrc/af_tower_bf16.hip, Geo<15>): both ways of handing it weights write the
 same bytes, the whole net meets the bar the 11x11 net is held to, and it plugs into the self-play engine and the training loop."""
+import functools
+
 import numpy as np
 import pytest
 
+import tower_gpu
 from conftest import make_cfg
+from tower_gpu import same_bits
 
 pytestmark = pytest.mark.gpu
 S, W, NPIX = 15, 128, 225
-
-
-def planes(n, seed=1):
-    """Random-stone positions: [n, 3, 15, 15] of 0 / 1 (own stones, opponent's stones, side to move)."""
-    import torch
-    rng = np.random.default_rng(seed)
-    x = np.zeros((n, 3, S, S), np.float32)
-    stones = rng.integers(0, 3, size=(n, S, S))
-    x[:, 0], x[:, 1] = stones == 1, stones == 2
-    x[:, 2] = rng.integers(0, 2, size=(n, 1, 1))
-    return torch.from_numpy(x).cuda()
+planes = functools.partial(tower_gpu.planes, S=S)    # random-stone positions [n, 3, 15, 15]
 
 
 def weight_set(net, seed):
@@ -33,11 +27,6 @@ def weight_set(net, seed):
             a = (rng.random(shape) * 2 - 1) * np.sqrt(3.0 / fan)
         out[name] = torch.from_numpy(a.astype(np.float32)).bfloat16().float().numpy()
     return out
-
-
-def same_bits(a, b):
-    import torch
-    return all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
 
 
 def test_host_setters_and_device_update_write_the_same_bytes():

@@ -11,14 +11,19 @@ room) the fp32 values on which a bf16 conversion can go wrong: exact ties that r
 mantissa, both signs; +0 and -0; a denormal (1e-40); and — except in the sets a forward runs on — +-3.39e38 (the largest finite
 bf16 after rounding), +-3.4e38 (inf after rounding) and, in the kernels, four NaNs."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+import tower_gpu
+from tower_gpu import same_bits
 
 pytestmark = pytest.mark.gpu
 
 S, W, BLOCKS, MAXB = 11, 128, 2, 32
 NBUF = 4 * BLOCKS + 12
+planes = functools.partial(tower_gpu.planes, S=S)    # random-stone positions [n, 3, 11, 11]
 
 
 def _f32(bits):
@@ -107,17 +112,6 @@ def on_device(V):
     return {k: torch.from_numpy(v).cuda() for k, v in V.items()}
 
 
-def planes(n, seed=1):
-    """Random-stone positions: [n, 3, 11, 11] of 0 / 1 (own stones, opponent's stones, side to move)."""
-    import torch
-    rng = np.random.default_rng(seed)
-    x = np.zeros((n, 3, S, S), np.float32)
-    stones = rng.integers(0, 3, size=(n, S, S))
-    x[:, 0], x[:, 1] = stones == 1, stones == 2
-    x[:, 2] = rng.integers(0, 2, size=(n, 1, 1))
-    return torch.from_numpy(x).cuda()
-
-
 def forward(tw, x):
     """DeepResNet.eval_hip over the handle: stem -> tower -> heads -> dense; clones of (policy, value)."""
     from alphafive_amd.network_deep import DeepResNet
@@ -125,11 +119,6 @@ def forward(tw, x):
     net._tower = tw
     p, v = net.eval_hip(x)
     return p.clone(), v.clone()
-
-
-def same_bits(a, b):
-    import torch
-    return all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
 
 
 @pytest.fixture(scope="module")

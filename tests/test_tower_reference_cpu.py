@@ -1,15 +1,17 @@
 """oracle/tower_fp64.py (the fp64 restatement the bf16 tower kernels are held to) checked without a GPU:
-(a) against torch's float64 convolution / linear ops on random data, and (b) that the exact-regime generators of
-tests/test_gpu_tower_exact.py meet the conditions under which a bf16 MFMA kernel must reproduce fp64 bit for bit."""
+(a) against torch's float64 convolution / linear ops on random data, and (b) that the 11x11 exact-regime cases of
+tests/tower_cases.py meet the conditions, stated there, under which a bf16 MFMA kernel must reproduce fp64 bit for bit."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-import test_gpu_tower_exact as gen
+import tower_cases as gen
 from oracle import tower_fp64 as ref64
 
-S, W, NPIX = gen.S, gen.W, gen.NPIX
+S, W = 11, gen.W
+NPIX = gen.SIZES[S].NPIX
+
 
 
 def _close(a, b):
@@ -69,74 +71,18 @@ def test_reference_layers_match_torch_float64():
     _close(policy, torch.softmax(tl, dim=1))
 
 
-def _integers_in(a, lo, hi):
-    return bool((a == np.rint(a)).all() and a.min() >= lo and a.max() <= hi)
-
-
 @pytest.mark.parametrize("iso", gen.ISOLATIONS)
 def test_exact_block_generators_meet_the_exactness_conditions(iso):
-    case = gen.exact_block_case(iso)
-    h = case["h"]
-    g, A1, out, A2 = gen.exact_block_reference(iso)
-    assert A1.max() <= 256 and A2.max() <= 256
-    assert _integers_in(g, 0, 256) and _integers_in(out, 0, 256) and _integers_in(h, 0, 256)
-    assert (h[:NPIX] != 0).any(axis=0).all()                         # every (cin, pixel) site is non-zero in some position
-    for c in range(W):                                               # no two positions share an input plane
-        assert len(np.unique(h[:, c].reshape(gen.NPOS, NPIX), axis=0)) == gen.NPOS
-    for k in ("c1", "c2", "res"):
-        assert set(np.unique(case[k][0])) <= {-1.0, 0.0, 1.0} and _integers_in(case[k][1], -256, 256)
-    # what the isolation is for: distinct biases per cout on the convolution under test, and an output that depends on it
-    total = case["c2"][1] + case["res"][1]
-    if iso == "conv1":
-        assert len(set(case["c1"][1])) == W and not total.any() and case["res"][1].all() and np.array_equal(out, g)
-    else:
-        assert len(set(total)) == W and case["res"][1].all() and case["c2"][1].all()
-        assert np.array_equal(g, h) if iso == "conv2" else not case["c2"][0].any()
-    assert len(np.unique(out.reshape(gen.NPOS, -1), axis=0)) == gen.NPOS    # a stale buffer (another position's result) shows
-    assert out.std() > 5                                             # ... and the outputs are not just the biases
+    gen.check_exact_block_generator(S, iso)
 
 
 def test_exact_stem_generator_meets_the_exactness_conditions():
-    c = gen.exact_stem_case()
-    y, A = ref64.stem(c["planes"], c["w"], c["b"])
-    assert A.max() <= 256 and _integers_in(y, 0, 256)
-    assert set(np.unique(c["planes"])) == {0.0, 1.0} and set(np.unique(c["w"])) == {-1.0, 0.0, 1.0} and len(set(c["b"])) == W
-    p = c["planes"]
-    assert p[0].all() and not p[1].any() and len(np.unique(p.reshape(gen.NDIST, -1), axis=0)) == gen.NDIST
-    single = p[p.reshape(gen.NDIST, -1).sum(1) == 1]
-    for cin in range(3):                                             # a single stone at every corner and edge of every plane
-        for (yy, xx) in ((0, 0), (0, S - 1), (S - 1, 0), (S - 1, S - 1), (0, 5), (5, 0), (S - 1, 5), (5, S - 1)):
-            assert single[:, cin, yy, xx].any()
-    assert (np.abs(c["w"]).sum(axis=0) > 0).all()                    # every one of the 75 taps carries weight for some cout
+    gen.check_exact_stem_generator(S)
 
 
 def test_exact_heads_generator_meets_the_exactness_conditions():
-    c = gen.exact_heads_case()
-    vin, Av, pin, Ap = ref64.heads(c["h"], c["vconv"], c["pconv"])
-    assert Av.max() <= 256 and Ap.max() <= 256 and _integers_in(vin, 0, 256) and _integers_in(pin, 0, 256)
-    assert _integers_in(c["h"], 0, 256) and (c["h"] != 0).any(axis=0).all()
-    assert len(np.unique(c["h"].reshape(gen.NDIST, -1), axis=0)) == gen.NDIST
-    assert len(set(c["vconv"][1]) | set(c["pconv"][1])) == 20         # 20 distinct biases over the two heads
+    gen.check_exact_heads_generator(S)
 
 
 def test_exact_dense_generator_meets_the_exactness_conditions():
-    c = gen.exact_dense_case()
-    policy, value, logits, z = ref64.dense(c["vin"], c["pin"], c["vfc1"], c["vfc2"], c["pfc"])
-    assert _integers_in(c["vin"], 0, 256) and _integers_in(c["pin"], 0, 256)
-    assert _integers_in(logits * 4, -64, 64)                         # multiples of 2^-2, |logit| <= 16
-    assert (np.abs(z) < 3).mean() >= 0.9                             # tanh is not saturated
-    v1 = c["vin"] @ c["vfc1"][0] + c["vfc1"][1]
-    av1 = np.abs(c["vin"]) @ np.abs(c["vfc1"][0]) + np.abs(c["vfc1"][1])
-    assert _integers_in(v1, 0, 2 ** 24) and av1.max() < 2 ** 24      # fc1 stays on the ELU's x >= 0 side and is exact in fp32
-    az = av1 @ np.abs(c["vfc2"][0])[:, 0] + abs(c["vfc2"][1][0])
-    assert _integers_in(z * 2 ** 12, -2 ** 24, 2 ** 24) and az.max() * 2 ** 12 < 2 ** 24     # z: multiples of 2^-12 below 2^12
-    al = np.abs(c["pin"]) @ np.abs(c["pfc"][0]) + np.abs(c["pfc"][1])
-    assert al.max() * 4 < 2 ** 24
-    assert set(np.unique(c["vfc2"][0] * 2 ** 12)) == {-1.0, 0.0, 1.0} and c["vfc2"][1][0] != 0
-    assert set(np.unique(c["pfc"][0] * 4)) == {-1.0, 0.0, 1.0} and _integers_in(c["pfc"][1] * 4, -64, 64) and c["pfc"][1].any()
-    for name in ("vin", "pin"):
-        assert len(np.unique(c[name], axis=0)) == gen.NDIST
-    for w in (c["vfc1"], c["vfc2"], c["pfc"]):                       # the packers round to bf16: nothing may change
-        assert np.array_equal(ref64.bf16_round(w[0]), w[0]) and np.array_equal(ref64.bf16_round(w[1]), w[1])
-    assert len(np.unique(np.round(value, 6))) > gen.NDIST // 2 and value.std() > 1e-3       # the positions do differ in value
-    assert (policy.max(axis=1) > 0.05).all()                         # peaked enough that seven stray exp(0 - max) terms would show
+    gen.check_exact_dense_generator(S)
