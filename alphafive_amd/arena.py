@@ -244,7 +244,7 @@ def play_matches_device(cfg, pv0, pv1, n_games, device=0, seed0=0, seed1=1, node
         a.close()
 
 
-def ladder(cfg, ckpt_paths, games, match_fn=None, result_path=None, log=print):
+def ladder(cfg, ckpt_paths, games, match_fn=None, result_path=None, log=print, net_factory=None):
     """The bracket of choose_best_player.py:37-85 over checkpoints ordered oldest to newest: low, high = 0, len - 1; while low < high
     ckpt[low] (player 0) plays ckpt[high] (player 1) `games` games; wins0 < wins1 drops the low one (low += 1, player 0 takes the next
     checkpoint), anything else — a tie included — drops the high one (high -= 1, player 1 takes the previous one).  After every
@@ -253,12 +253,14 @@ def ladder(cfg, ckpt_paths, games, match_fn=None, result_path=None, log=print):
 
     match_fn(path0, path1, games) -> (w0, w1, draws).  Default: one DeviceArena of `games` slots, reused across the pairings, over
     two ResNets on the hip backend whose weights are swapped with ResNet.restore (a ".npz" path: load_npz / set_variables).
+    net_factory: what the default match_fn builds its two nets with instead of ResNet(cfg.board_size) — for a bracket over deep
+    checkpoints, lambda: DeepResNet(S, blocks, 128); its .npz files are loaded in place into the nets' evaluators.
     Not reproduced: the reference plays the games of a pairing one after the other and breaks off after 30 of them at a 2:1 score
     (:65-72); a batch of simultaneous games has no "after 30 games", so every pairing plays all its games."""
     paths = list(ckpt_paths)
     own = None
     if match_fn is None:
-        own = match_fn = _arena_match_fn(cfg, games)
+        own = match_fn = _arena_match_fn(cfg, games, net_factory=net_factory)
     out = []
     low, high = 0, len(paths) - 1
     try:
@@ -282,8 +284,9 @@ def ladder(cfg, ckpt_paths, games, match_fn=None, result_path=None, log=print):
     return out
 
 
-def _arena_match_fn(cfg, games, device=0):
-    """ladder's default match_fn: the nets and the arena are built at the first pairing and kept."""
+def _arena_match_fn(cfg, games, device=0, net_factory=None):
+    """ladder's default match_fn: the nets and the arena are built at the first pairing and kept.  net_factory() -> a net; a
+    DeepResNet plays through an evaluator of its own for `games` slots, a ResNet through select_backend("hip")."""
     state = {}
 
     def load(net, path):
@@ -294,11 +297,13 @@ def _arena_match_fn(cfg, games, device=0):
 
     def match(path0, path1, n):
         from .network import ResNet
+        from .network_deep import DeepResNet
         if not state:
-            state["nets"] = [ResNet(cfg.board_size, device="cuda:%d" % device) for _ in range(2)]
+            make = net_factory or (lambda: ResNet(cfg.board_size, device="cuda:%d" % device))
+            state["nets"] = [make() for _ in range(2)]
             state["loaded"] = [None, None]
-            state["arena"] = DeviceArena(cfg, state["nets"][0].select_backend("hip"), state["nets"][1].select_backend("hip"), n,
-                                         device=device)
+            pvs = [net.evaluator(n) if isinstance(net, DeepResNet) else net.select_backend("hip") for net in state["nets"]]
+            state["arena"] = DeviceArena(cfg, pvs[0], pvs[1], n, device=device)
         for p, path in enumerate((path0, path1)):
             if state["loaded"][p] != path:               # the bracket moves one end at a time: the other net keeps its weights
                 load(state["nets"][p], path)

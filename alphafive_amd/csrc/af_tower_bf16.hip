@@ -1,13 +1,16 @@
 // af_tower_bf16.hip — bf16 residual tower for gfx950 (C ABI: include/af_tower_bf16.h).
 //
-// Two kernels, af_tower_conv<G, PROJ, DEPTH> and af_tower_conv3<G, PROJ, DEPTH>, compute the same 3x3 convolution 128 -> 128 over
+// Three kernels compute the same 3x3 convolution: af_tower_conv<G, PROJ, DEPTH> and af_tower_conv3<G, PROJ, DEPTH>, weight-stationary
+// and persistent, which af_tower_forward launches, and af_tower_conv_small<G, PROJ>, one workgroup per pixel tile with the weights
+// streamed, which af_tower_forward_small launches for a handful of positions (its own comment, behind af_tower_conv3; the same
+// bits).  The first two are described here: they compute the 3x3 convolution 128 -> 128 over
 // 11x11 boards (G = Geo<11>; what follows describes that geometry — Geo<15>, which af_tower_conv alone runs, on half boards, is
 // described at the geometry types) as an implicit GEMM
 //   out[cout][pixel] = sum_{tap, cin} W[cout][cin][tap] * in[cin][pixel + tap offset]
 // on v_mfma_f32_32x32x16_bf16 (M = 32 couts, N = 32 pixels, K = 16 cin of one tap), plus, for the second
 // convolution of a block (PROJ), 8 more k-steps that fold the block's 1x1 projection of the block input in.
-// They share everything described below — set-up, staging, LDS layout, tap addresses: the functions in front of them — and
-// differ in their position loops only: af_tower_conv runs a position's MFMAs over four accumulator sets and then its epilogue;
+// They share everything described below — set-up, staging, LDS layout, tap addresses: the functions in front of them, which
+// af_tower_conv_small calls too — and differ in their position loops only: af_tower_conv runs a position's MFMAs over four accumulator sets and then its epilogue;
 // af_tower_conv3 runs two phases of two pixel tiles and issues the finished pair's epilogue inside the other pair's MFMA stream
 // (see its own comment).  Which one runs where is tune key 3 (kConv / pick in the host part): by default af_tower_conv3 for a
 // block's first convolution and af_tower_conv for its second (PROJ); 0 = af_tower_conv for both, at the ring depth of key 0;
@@ -560,6 +563,104 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv3(TowerArgs A) {
     for (int c = 0; c < 16; ++c)
 #pragma unroll
         for (int k = 0; k < kEpiK; ++k) epi_stage(2, c, k, o_prev);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// af_tower_conv_small<G, PROJ>: the same convolution for a handful of positions (af_tower_forward_small).  The two kernels above
+// are weight-stationary: a workgroup loads its 295 / 328 KB of A fragments before its first MFMA and then walks positions, which at
+// batch 1 is one workgroup on one CU doing 288 / 320 MFMAs per wave behind that load.  Here the work is split the other way:
+//   - one workgroup per (pseudo-position, pixel tile): grid = batch * HALVES * 4, workgroup b = tile b & 3 of pseudo-position b >> 2;
+//     its 4 waves are the 4 cout tiles of 32, as above;
+//   - the workgroup stages its pseudo-position's plane (PROJ: and the block-input plane) once, single-buffered, into the same LDS
+//     layout with the same stage_first / stage_round, so proj_tap / conv_tap and the edge / zero-region bases are the ones above;
+//   - a wave runs its ONE pixel tile's 72 / 80 MFMAs into ONE accumulator, in tower_layer's per-accumulator order (PROJ: projection
+//     steps 0..7, then tap 0..8 major, cin step 0..7 minor) — a single chain of v_mfma_f32_32x32x16_bf16 issues at the MFMA rate;
+//   - the A fragments are not resident: fragment i of that order streams from the packed buffer (the very stream load_weights
+//     reads) through a ring of kSmallA register sets, its load issued kSmallA MFMAs before its use, so the first MFMA waits for the
+//     planes and ONE fragment, not for all of them.  The prefill is issued behind the staging loads and in front of the wait, which
+//     counts them out: loads return in order, so vmcnt(kSmallA) means every LDS-DMA piece has landed;
+//   - the epilogue is tower_layer's for that tile: elu2(acc + bias), bf16, the same two 16-byte stores at the same addresses, for
+//     the lanes whose pixel exists in this (half-)board.
+// Same MFMAs on the same operands in the same order, the same epilogue arithmetic: bit-identical to af_tower_conv (and, where that
+// is, to af_tower_conv3).  Workgroups are independent: no hand-over, no waiting on each other, no atomics.
+// The block's second convolution runs in place (out = in2 = x), and the four tile workgroups of a position (times two halves) run
+// concurrently, so a workgroup may stage units of x that a sibling has already overwritten.  This is the situation argued above
+// tower_layer for the two halves, one level finer: x is read only through the 1x1 projection at the lane's OWN pixel (proj_tap: the
+// centre unit of a pixel this workgroup computes and nobody else writes); the 3x3 window reads g, which this launch does not
+// write.  A lane whose pixel does not exist reads another tile's unit (pixel 0's, or a row of the other half): whatever it finds,
+// its result is never stored.
+constexpr int kSmallA = 32;      // A-fragment ring: 32 KB per wave in flight (a CU's share of the bandwidth x the latency of a miss)
+constexpr int kSmallB = 8;       // B-fragment ring, as af_tower_conv's at depth 8
+template <class G, bool PROJ>
+__global__ __launch_bounds__(256) void af_tower_conv_small(TowerArgs A) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];         // [256 B][g][-]([h])[zero region]: Lay<G>'s, one plane unused
+    constexpr int NS = PROJ ? 80 : 72, NPJ = PROJ ? 8 : 0;
+    static_assert(kSmallA <= 63 && kSmallA <= NS, "the ring's prefill is counted on vmcnt");
+    using L = Lay<G>;
+    const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
+    const int pos = (int)(blockIdx.x >> 2), j = (int)(blockIdx.x & 3);  // pseudo-position (< batch * HALVES by the grid), pixel tile
+    stage_first<G, PROJ>(A, smem, lds0, wv, pos);
+    // A fragment of MFMA i: the projection's (72..79 of the stream) first
+    const uint4* wp = A.w + ((size_t)wv * NS * 64 + lane);
+    auto frag = [&](int i) -> bf16x8 {
+        const uint4 v = wp[(i < NPJ ? 72 + i : i - NPJ) * 64];
+        bf16x8 f;
+        __builtin_memcpy(&f, &v, 16);
+        return f;
+    };
+    bf16x8 ra[kSmallA];
+#pragma unroll
+    for (int i = 0; i < kSmallA; ++i) ra[i] = frag(i);
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(kSmallA) : "memory");    // planes landed, zero region written
+    __builtin_amdgcn_s_barrier();
+    float bias_r[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bias_r[r] = A.bias[32 * wv + 16 * kg + r];
+    // the lane's pixel of tile j: pixel_bases and tap_bases for that one tile
+    const int n = 32 * j + nn;
+    const bool ok = n < G::HPIX0;
+    const int nc = ok ? n : 0;
+    const bool live = ok && (G::HALVES == 1 || !(pos & 1) || n < G::HPIX1);
+    const int px = nc % G::S;
+    const uint32_t lb = kLds0 + (uint32_t)(kg * G::LPIX + nc + G::S - (G::S + 1)) * 16u;
+    const uint32_t ob = (uint32_t)(nc + G::S) * 16u;
+    const uint32_t zb = L::zero_off(PROJ) + (lb & 255u);
+    const uint32_t bC = !live ? zb : lb, bL = px == 0 ? zb : bC, bR = px == G::S - 1 ? zb : bC;
+    auto rd = [&](int i) -> bf16x8 {
+        if (i < NPJ) return proj_tap<G>(smem, lb, i);
+        const int s_ = i - NPJ, t = s_ >> 3;
+        return conv_tap<G>(smem, t % 3 == 0 ? bL : (t % 3 == 2 ? bR : bC), t, s_ & 7);
+    };
+    bf16x8 rb[kSmallB];
+#pragma unroll
+    for (int i = 0; i < kSmallB; ++i) rb[i] = rd(i);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    __builtin_amdgcn_sched_barrier(0);                       // the ring's first reads stay in front: the groups below would take them one by one
+#pragma clang loop unroll(full)
+    for (int i = 0; i < NS; ++i) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[i % kSmallA], rb[i % kSmallB], acc, 0, 0, 0);
+        if (i + kSmallB < NS) rb[i % kSmallB] = rd(i + kSmallB);
+        if (i + kSmallA < NS) ra[i % kSmallA] = frag(i + kSmallA);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+    }
+    char* const o = G::HALVES == 1 ? A.out + (size_t)pos * L::kPlaneB
+                                   : A.out + (size_t)(pos >> 1) * L::kPlaneB + (uint32_t)((pos & 1) * G::HOFF) * 16u;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        bf16x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            const f32x2 y = elu2(f32x2{acc[8 * hf + e], acc[8 * hf + e + 1]} + f32x2{bias_r[8 * hf + e], bias_r[8 * hf + e + 1]});
+            v[e] = (__bf16)y.x; v[e + 1] = (__bf16)y.y;
+        }
+        if (live) *reinterpret_cast<bf16x8*>(o + (uint32_t)((4 * wv + 2 * kg + hf) * G::PIX) * 16u + ob) = v;
+    }
 }
 
 // (r2 A/B record, removed from the source in r6: af_tower_conv2, the same convolution on af_conv_f16s.hip's slab-ring structure —
@@ -1326,6 +1427,23 @@ static const ConvKernel* pick(int S, int engine, bool second, int depth) {
     return nullptr;         // (not reached with the values af_tower_tune accepts)
 }
 
+// af_tower_forward_small's kernels: one per geometry and convolution of a block, in Lay<G>'s LDS layout.
+struct SmallKernel {
+    void (*fn)(TowerArgs);
+    int S;
+    bool proj;
+    uint32_t lds;
+};
+constexpr SmallKernel kSmall[4] = {
+    {af_tower_conv_small<G11, false>, 11, false, Lay<G11>::lds_bytes(false)}, {af_tower_conv_small<G11, true>, 11, true, Lay<G11>::lds_bytes(true)},
+    {af_tower_conv_small<G15, false>, 15, false, Lay<G15>::lds_bytes(false)}, {af_tower_conv_small<G15, true>, 15, true, Lay<G15>::lds_bytes(true)},
+};
+// af_tower_small_batch: the largest batch up to which the whole forward was measured faster on af_tower_forward_small than on
+// af_tower_forward, per board size (profiles/tower_small_batch.md: medians apart by more than both forms' min..max spread; measured
+// at 1, 2, 4, ... 256: at 11x11 the small form wins by 45 us of 211 at 64 and loses at 128, at 15x15 it wins by 37 of 245 at 32 and
+// loses at 64 — where its grid passes one workgroup per CU)
+constexpr int32_t kSmallBatch11 = 64, kSmallBatch15 = 32;
+
 static TowerArgs layer_args(const af_tower* t, int b, bool second, void* x, void* g, int batch) {
     TowerArgs a;
     a.in = static_cast<const char*>(second ? g : x);
@@ -1363,6 +1481,8 @@ static int allocate(af_tower* t) {
     TW_HIP_OK(hipSetDevice(t->device));
     TW_HIP_OK(hipDeviceGetAttribute(&t->ncu, hipDeviceAttributeMultiprocessorCount, t->device));
     for (const ConvKernel& k : kConv)
+        TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const SmallKernel& k : kSmall)
         TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int n = 4 * t->blocks + kEnds;
     auto padded = [](int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); };
@@ -1516,6 +1636,23 @@ int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
+
+int af_tower_forward_small(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch) {
+    if (!t || !x_dev || !g_dev || batch < 1) return AF_TOWER_ERR_ARG;
+    for (int b = 0; b < t->blocks; ++b) if (!t->set[b]) return AF_TOWER_ERR_STATE;
+    const int64_t grid = (int64_t)batch * t->d.halves * 4;    // one workgroup per pixel tile of a (half-)position
+    if (grid > INT32_MAX) return AF_TOWER_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int b = 0; b < t->blocks; ++b)
+        for (int second = 0; second < 2; ++second)
+            for (const SmallKernel& k : kSmall)
+                if (k.S == t->S && k.proj == (second != 0))
+                    hipLaunchKernelGGL(k.fn, dim3((unsigned)grid), dim3(256), k.lds, st, layer_args(t, b, second != 0, x_dev, g_dev, batch));
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
+
+int32_t af_tower_small_batch(const af_tower* t) { return !t ? 0 : t->S == 11 ? kSmallBatch11 : kSmallBatch15; }
 
 #ifdef AF_TOWER_TIMING
 int af_tower_debug_cycles(unsigned long long* host) {

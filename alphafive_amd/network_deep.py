@@ -8,6 +8,8 @@ it, random init, no bit parity); it plugs into SelfPlayEngine through the same
 planes[G,3,S,S] -> (prob[G,C], value[G]) evaluator seam as the fp32 net.
 """
 import collections
+import threading
+import weakref
 
 import numpy as np
 import torch
@@ -31,22 +33,32 @@ def variable_shapes(board_size, blocks=8, width=128):
 
 
 class _HipEvaluator(object):
-    """planes -> (prob, value) on the hand-written kernels; bind_outputs lets the engine own the result tensors."""
+    """planes -> (prob, value) on the hand-written kernels; bind_outputs lets the engine own the result tensors.  An evaluator
+    owns its tower — handle, packed weights, activation buffers, bound outputs — so every consumer of a net (a Player, a self-play
+    engine, an arena) has one of its own; the net re-packs all of them when its weights change (DeepResNet._towers)."""
 
-    def __init__(self, net):
-        self.net = net
+    def __init__(self, net, tower):
+        self.net, self.tower = net, tower
 
     def __call__(self, x):
-        return self.net.eval_hip(x)
+        return self.net.eval_hip(x, self.tower)
 
     def bind_outputs(self, policy, value):
-        if policy.shape[0] >= self.net._tower.max_batch:
-            self.net._tower.bind_outputs(policy, value)
+        if policy.shape[0] >= self.tower.max_batch:
+            self.tower.bind_outputs(policy, value)
 
     def weights_version(self):
         """What a captured graph of this evaluator is keyed on (SelfPlayEngine.run_ticks_graph): the net's pack counter, which
-        select_backend() and every re-pack of the tower's weights, from the host or on the device, bump."""
+        select_backend() and every re-pack of the towers' weights, from the host or on the device, bump."""
         return self.net._pack_version
+
+    def close(self):
+        """Releases the tower and leaves the net's registry.  The net's primary evaluator (select_backend) takes net._tower along."""
+        self.net._evaluators.discard(self)
+        if getattr(self.net, "_tower", None) is self.tower:
+            self.net._tower = None
+        if self.tower is not None:
+            self.tower.close()
 
 
 class DeepResNet(object):
@@ -69,6 +81,23 @@ class DeepResNet(object):
         self.vconv, self.pconv = (glorot(4, width, 1, 1), z(4)), (glorot(16, width, 1, 1), z(16))
         self.vfc1, self.vfc2 = (glorot(4 * C, 64), z(64)), (glorot(64, 1), z(1))
         self.pfc = (glorot(16 * C, C), z(C))
+        self._pack_version = 0
+        self._evaluators = weakref.WeakSet()     # live evaluators: an evaluator dropped without close() frees its tower by itself
+        self._eval_lock = threading.Lock()       # eval(): one evaluator of the net's own, its outputs copied out before the next call
+        self._own_eval = None
+
+    @property
+    def version(self):
+        """The pack counter: moves with every weight update (what Player._weights_version keys its captured graph on)."""
+        return self._pack_version
+
+    def _towers(self):
+        """Every live tower over this net: the primary one (select_backend) and those of the evaluators handed out."""
+        out = []
+        for tw in [getattr(self, "_tower", None)] + [e.tower for e in list(getattr(self, "_evaluators", ()))]:
+            if tw is not None and tw._h and all(tw is not o for o in out):
+                out.append(tw)
+        return out
 
     # ---- weights by name ----
     def variable_shapes(self):
@@ -117,14 +146,13 @@ class DeepResNet(object):
             new[name] = v.to(device=self.device, dtype=self.dtype).contiguous()
         for name, (holder, key, i) in self._named().items():
             holder[key] = tuple(new[name] if k == i else t for k, t in enumerate(holder[key]))
-        tower = getattr(self, "_tower", None)
-        if tower is not None:
+        for tower in self._towers():
             for b, blk in enumerate(self.tower):
                 tower.set_block(b, blk)
             tower.set_stem(self.stem)
             tower.set_heads(self.vconv, self.pconv)
             tower.set_dense(self.vfc1 + self.vfc2 + self.pfc)
-            self._pack_version = getattr(self, "_pack_version", 0) + 1
+        self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     @torch.no_grad()
     def set_variables_device(self, tensors):
@@ -135,8 +163,8 @@ class DeepResNet(object):
         biases from small fp32 temporaries made of the net's rounded copies.  The tower adds the stem's, blocks' and head
         convolutions' biases in fp32 as given, so handing over the rounded values is what makes host path and device path pack
         the same values and give the same bits.  A cpu net, or one without a hip backend, does what set_variables does."""
-        tower = getattr(self, "_tower", None)
-        if self.device.type != "cuda" or tower is None:
+        towers = self._towers()
+        if self.device.type != "cuda" or not towers:
             self.set_variables(tensors)
             return
         src = collections.OrderedDict()
@@ -147,7 +175,8 @@ class DeepResNet(object):
             own.copy_(src[name])
             if name.endswith("bias"):
                 src[name] = own.float()
-        tower.load_device(src)
+        for tower in towers:
+            tower.load_device(src)
         self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     def save_npz(self, path):
@@ -189,21 +218,65 @@ class DeepResNet(object):
             return self.eval_device
         if name != "hip":
             raise ValueError(name)
-        from . import tower_hip
         self._pack_version = getattr(self, "_pack_version", 0) + 1
-        self._tower = tower_hip.HipTower(self.tower, self.board_size, self.width, max_batch, self.device, stem=self.stem,
-                                         vconv=self.vconv, pconv=self.pconv, dense=self.vfc1 + self.vfc2 + self.pfc)
-        return _HipEvaluator(self)
+        ev = self.evaluator(max_batch)           # the net's primary evaluator: its tower is what eval_hip(x) runs on
+        self._tower = ev.tower
+        return ev
+
+    def evaluator(self, max_batch):
+        """A new evaluator with a tower of its own, packed from the net's current tensors: one per consumer, so that two Players,
+        or a Player and a self-play engine, share the net and not each other's buffers.  It follows set_variables /
+        set_variables_device / load_npz in place until its close() (or the net's)."""
+        from . import tower_hip
+        tower = tower_hip.HipTower(self.tower, self.board_size, self.width, max_batch, self.device, stem=self.stem,
+                                   vconv=self.vconv, pconv=self.pconv, dense=self.vfc1 + self.vfc2 + self.pfc)
+        ev = _HipEvaluator(self, tower)
+        self._evaluators.add(ev)
+        return ev
 
     @torch.no_grad()
-    def eval_hip(self, x):
-        """The whole forward on hand-written kernels: af_tower_stem -> af_tower_forward -> af_tower_heads (the 1x1 convs)
-        -> af_tower_dense (the three dense layers + softmax on the MFMA)."""
-        B, tw = x.shape[0], self._tower
+    def eval_hip(self, x, tower=None):
+        """The whole forward on hand-written kernels: af_tower_stem -> af_tower_forward[_small] -> af_tower_heads (the 1x1 convs)
+        -> af_tower_dense (the three dense layers + softmax on the MFMA), on `tower` (default: the primary evaluator's).
+        The one place that chooses the tower's form: the tile-parallel kernel up to the batch the library measured it faster at
+        (HipTower.small_batch), the persistent kernels above; the bits are the same either way."""
+        tw = self._tower if tower is None else tower
+        B = x.shape[0]
         tw.stem(x.contiguous())
-        tw.forward(B)
+        if B <= tw.small_batch:
+            tw.forward_small(B)
+        else:
+            tw.forward(B)
         tw.heads(B)
         return tw.dense(B)
+
+    def eval(self, inputs):
+        """network.py:90-97, as ResNet.eval: numpy float32[B,3,S,S] -> (prob[B,S*S], value[B]) numpy.  A cuda net evaluates on the
+        hand-written kernels through an evaluator of its own, made at the first call (and again for a larger batch); a cpu net
+        through eval_device."""
+        x = torch.from_numpy(np.ascontiguousarray(inputs, np.float32))
+        if self.device.type != "cuda":
+            p, v = self.eval_device(x)
+            return p.float().numpy(), v.float().numpy()
+        with self._eval_lock:
+            ev = self._own_eval
+            if ev is None or ev.tower is None or not ev.tower._h or ev.tower.max_batch < x.shape[0]:
+                if ev is not None:
+                    ev.close()
+                ev = self._own_eval = self.evaluator(max(int(x.shape[0]), 1))
+            p, v = ev(x.to(self.device))
+            return p.cpu().numpy(), v.cpu().numpy()
+
+    def close(self):
+        """Closes every evaluator the net handed out (their towers: handles, packed weights, buffers), the primary one included."""
+        for ev in list(self._evaluators):
+            ev.close()
+        self._own_eval = None
+        tower = getattr(self, "_tower", None)
+        if tower is not None:
+            tower.close()
+            self._tower = None
+        self._pack_version = getattr(self, "_pack_version", 0) + 1      # a graph captured over released buffers must not replay
 
     @torch.no_grad()
     def eval_hip_torch_dense(self, x):

@@ -116,19 +116,27 @@ class Player(object):
         # pv_fn = ResNet.eval on a cuda device (self_play.py:88, choose_best_player.py:38-40): the leaves stay on the device and
         # are evaluated by the hand-written kernels straight into the tensors the tick kernel reads — this Player gets its own
         # evaluator handle (its output buffers are bound to this game).  select_backend("hip") raises when libaf_net.so is
-        # missing or its ABI does not match; nothing falls back to vendor ops.  Any other owner with an eval_device() method
-        # (e.g. DeepResNet) is used as it is.
+        # missing or its ABI does not match; nothing falls back to vendor ops.  pv_fn = DeepResNet.eval on a cuda device: the
+        # same, through an evaluator of this Player's own (DeepResNet.evaluator(1): its own tower, so several Players and a
+        # self-play engine can share one net) — one leaf per simulation is the batch the tile-parallel tower kernel is for.
+        # Any other owner with an eval_device() method is used as it is.
         owner = getattr(pv_fn, "__self__", None)
         self._pv_owner = None
         self._pv_device = None
         self.backend = "host"                            # evaluations cross the host boundary (numpy pv_fn or pipe)
         self._use_graph = bool(graph)
         self._graph = None
+        self._pv_close = None                            # an evaluator this Player made and close() releases
         if pv_fn is not None and owner is not None and getattr(pv_fn, "__name__", "") == "eval" \
                 and hasattr(owner, "eval_device") and getattr(getattr(owner, "device", None), "type", None) == "cuda":
             from .network import ResNet
+            from .network_deep import DeepResNet
             if isinstance(owner, ResNet):
                 fn = owner.select_backend("hip")
+                fn.bind_outputs(self._policy, self._value)
+                self._pv_device, self._pv_owner, self.backend = fn, owner, "hip"
+            elif isinstance(owner, DeepResNet):
+                fn = self._pv_close = owner.evaluator(1)
                 fn.bind_outputs(self._policy, self._value)
                 self._pv_device, self._pv_owner, self.backend = fn, owner, "hip"
             else:
@@ -313,4 +321,8 @@ class Player(object):
         if self._engine is not None:
             self._engine.close()
             self._engine = None
+        if self._pv_close is not None:
+            self._graph = None                           # (captured over the evaluator's buffers)
+            self._pv_close.close()
+            self._pv_close = None
         gc.collect()

@@ -42,6 +42,9 @@ def lib():
         L.af_tower_plane_elems.argtypes = [vp]
         L.af_tower_plane_elems.restype = C.c_int64
         L.af_tower_forward.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.af_tower_forward_small.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.af_tower_small_batch.argtypes = [vp]
+        L.af_tower_small_batch.restype = C.c_int32
         L.af_tower_flops_per_position.argtypes = [vp]
         L.af_tower_flops_per_position.restype = C.c_int64
         L.af_tower_tune.argtypes = [C.c_int32, C.c_int32]
@@ -97,6 +100,7 @@ class HipTower(object):
         self.pin = torch.empty((max_batch, 16 * board_size ** 2), dtype=torch.bfloat16, device=self.device)
         self.pix = int(lib().af_tower_pix(self._h))
         self.flops_per_position = int(lib().af_tower_flops_per_position(self._h))
+        self.small_batch = int(lib().af_tower_small_batch(self._h))       # forward_small is the faster form up to this batch (0: never)
         # C8 activations [B][width/8][PIX][8]; zero borders are never written by the kernels
         self.x = torch.zeros((max_batch, width // 8, self.pix, 8), dtype=torch.bfloat16, device=self.device)
         self.g = torch.zeros_like(self.x)
@@ -173,6 +177,11 @@ class HipTower(object):
     def forward(self, B):
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().af_tower_forward(self._h, stream, self.x.data_ptr(), self.g.data_ptr(), B), "af_tower_forward")
+
+    def forward_small(self, B):
+        """forward() on the tile-parallel kernel (af_tower_forward_small): the same bits at any batch, faster up to small_batch."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_forward_small(self._h, stream, self.x.data_ptr(), self.g.data_ptr(), B), "af_tower_forward_small")
 
     def load_device(self, tensors):
         """Weight update without the host (af_tower_update_device): `tensors` is a list in the ABI's order or a dict by the names

@@ -67,6 +67,14 @@ int64_t af_tower_plane_elems(const af_tower* t);   /* bf16 elements per position
 /* Runs all blocks in place on x_dev (C8 bf16, zero borders); g_dev is scratch of the same size whose
  * borders must be zero as well.  Asynchronous on `stream` (hipStream_t; NULL = default stream). */
 int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch);
+/* af_tower_forward on the tile-parallel kernel: same arguments, same contract (in place on x_dev, g_dev scratch, zero
+ * borders never written, asynchronous on `stream`, launches only, legal under stream capture), same bits.  Any batch >= 1.
+ * One workgroup per pixel tile of a (half-)position with the weights streamed from memory, where af_tower_forward keeps them
+ * resident in persistent workgroups: the form for a handful of positions.  Tune keys 0 - 3 do not reach it. */
+int af_tower_forward_small(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch);
+/* The largest batch at which the library's measurement found af_tower_forward_small faster than af_tower_forward on this
+ * handle's board size (0: never).  A constant per board size; where it was measured: profiles/tower_small_batch.md. */
+int32_t af_tower_small_batch(const af_tower* t);
 
 /* planes_dev float32[batch][3][S][S] (utils.py:256 layout) -> x_dev (C8 bf16; its zero rows are left untouched). */
 int af_tower_stem(af_tower* t, void* stream, const float* planes_dev, void* x_dev, int32_t batch);
