@@ -966,7 +966,23 @@ int af_net_forward(af_net* n, void* stream, const float* planes, int32_t batch, 
 }
 
 int af_net_debug_activation(af_net* n, int32_t which, int32_t batch, float* host_out) {
-    if (!n || !host_out || !n->f16s) return AF_NET_ERR_ARG;
+    if (!n || !host_out) return AF_NET_ERR_ARG;
+    if (which >= 16) {       // the fp32 planes act[]: 16 + i the interior [batch][C][S*S], 32 + i the buffer as stored [batch][C][PP]
+        const bool stored = which >= 32;
+        const int i = which - (stored ? 32 : 16);
+        if (i >= kActs || batch < 1 || batch > n->max_batch) return AF_NET_ERR_ARG;
+        const int C = act_channels(i), S = n->S, WP = n->WP, PP = n->PP;
+        const size_t count = (size_t)batch * C * PP;
+        NET_HIP_OK(hipSetDevice(n->device));
+        NET_HIP_OK(hipDeviceSynchronize());
+        if (stored) { NET_HIP_OK(hipMemcpy(host_out, n->act[i], count * sizeof(float), hipMemcpyDeviceToHost)); return C; }
+        std::vector<float> h(count);
+        NET_HIP_OK(hipMemcpy(h.data(), n->act[i], count * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t bc = 0; bc < (size_t)batch * C; ++bc)
+            for (int y = 0; y < S; ++y) memcpy(host_out + (bc * S + y) * S, h.data() + bc * PP + (y + 1) * WP + 1, S * sizeof(float));
+        return C;
+    }
+    if (!n->f16s) return AF_NET_ERR_ARG;
     const int c = f16s_read_activation(n->f16s, which, batch, host_out);
     return c < 0 ? AF_NET_ERR_ARG : c;
 }

@@ -132,6 +132,23 @@ class HipNet(object):
             raise NetError(f"af_net_debug_activation({idx}) returned {c} channels, expected {chans}")
         return out
 
+    # the fp32 path's planes (af_net_debug_activation's which = 16 + i, 32 + i) -> (i, channel count)
+    ACTIVATIONS_FP32 = {"f0": (0, 32), "g1": (1, 64), "o1": (2, 64), "g2": (3, 128), "o2": (4, 128), "g3": (5, 32), "o3": (6, 32),
+                        "g4": (7, 64), "o4": (8, 64), "g5": (9, 32), "o5": (10, 32)}
+
+    def debug_activation_fp32(self, name, batch, padded=False):
+        """Tests: plane `name` of ACTIVATIONS_FP32 of the fp32 Winograd path, any board size (synchronises): the interior as float32
+        [batch][C][S*S], or with padded=True the buffer as stored, [batch][C][PP] — board pixel (y, x) at (y + 1) WP + x + 1,
+        WP = 2 ceil(S/2) + 2, PP = WP*WP rounded up to a multiple of 16.  include/af_net.h lists which forwards write these."""
+        idx, chans = self.ACTIVATIONS_FP32[name]
+        WP = 2 * ((self.S + 1) // 2) + 2
+        out = np.empty((batch, chans, (WP * WP + 15) // 16 * 16 if padded else self.S * self.S), np.float32)
+        c = lib().af_net_debug_activation(self._h, (32 if padded else 16) + idx, batch, out.ctypes.data_as(C.POINTER(C.c_float)))
+        _check(c, "af_net_debug_activation")
+        if c != chans:
+            raise NetError(f"af_net_debug_activation({(32 if padded else 16) + idx}) returned {c} channels, expected {chans}")
+        return out
+
     def weights_version(self):
         """Count of load() and load_device() calls: what a captured graph over this handle (SelfPlayEngine.run_ticks_graph) is keyed on."""
         return self._version

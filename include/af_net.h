@@ -106,7 +106,16 @@ int af_net_tune(int32_t key, int32_t value);
  * 2^-22 relative, and to 2^-25 absolute below |f| ~ 2^-3 (fp16 subnormal halves are kept).  Beyond it the outputs are UNDEFINED and
  * may well be finite: the overflowed halves are inf / NaN, the next layer's sum is NaN, and the kernels' ELU (a max / min form)
  * maps NaN to -1.0.  Finite policy and value therefore do not show that a weight set is in range; the per-layer maxima of
- * oracle/net_fp64.intermediates do (shipped checkpoint: at most 376). */
+ * oracle/net_fp64.intermediates do (shipped checkpoint: at most 376).
+ *
+ * Tests of the fp32 path (af_net.hip), every board size, with or without a split-operand handle: the handle's fp32 planes, i = 0..10
+ * in the order f0, g1, o1, g2, o2, g3, o3, g4, o4, g5, o5 (32, 64, 64, 128, 128, 32, 32, 64, 64, 32, 32 channels):
+ *   which = 16 + i   the interior of plane i as fp32 [batch][C][S*S]
+ *   which = 32 + i   the same buffer exactly as stored, [batch][C][PP], WP = 2 ceil(S/2) + 2, PP = WP*WP rounded up to a multiple of
+ *                    16; board pixel (y, x) sits at (y + 1) WP + x + 1, everything else is border or pad, which no kernel writes
+ * Both return C; batch may be anything from 1 to max_batch, not only the last forward's (the buffers are sized for max_batch).
+ * Written by: conv path 1 (af_net_tune(0, 1), and every board size other than 11x11 / 15x15) all eleven; path 5 with key 9 = 0
+ * o3 and o5 only (the planes its branches end in for the fp32 heads); path 5 by default none. */
 int af_net_debug_activation(af_net* n, int32_t which, int32_t batch, float* host_out);
 
 /* Tests: weight-derived device buffer `index` copied to host_out (cap_bytes must hold it); returns its size in bytes (also when

@@ -1,11 +1,12 @@
-"""No GPU: the generators of tests/test_gpu_f16s_exact.py checked from oracle/net_fp64.py and a numpy model of the fp16 split alone —
-the conditions under which the split-operand kernels must reproduce fp64 bit for bit hold for every exact case, the envelope cases
-sit in the binades they claim, the shipped checkpoint keeps its headroom below fp16's maximum, and the exact comparison is sharp:
+"""No GPU: the generators of tests/net_cases.py, as tests/test_gpu_f16s_exact.py uses them, checked from oracle/net_fp64.py and a
+numpy model of the fp16 split alone — the conditions under which the split-operand kernels must reproduce fp64 bit for bit hold
+for every exact case, the envelope cases sit in the binades they claim, the shipped checkpoint keeps its headroom below fp16's maximum, and the exact comparison is sharp:
 a swapped weight row, a row-end neighbour that is not zeroed and a dropped lo half each change a compared value."""
 import numpy as np
 import pytest
 
-import test_gpu_f16s_exact as gen
+import net_cases as gen
+import test_gpu_f16s_exact as f16s
 from oracle import net_fp64
 
 
@@ -25,7 +26,7 @@ def _integral(a, q):
 
 
 def test_intermediates_end_in_the_bits_of_forward():
-    with np.load(gen.W6960) as z:
+    with np.load(f16s.W6960) as z:
         v = {k: z[k] for k in z.files}
     x = gen.board_positions(11, 6, seed=1)
     p, val = net_fp64.forward(v, x)
@@ -45,9 +46,9 @@ def test_intermediates_end_in_the_bits_of_forward():
 
 def test_pick_scale_restatement():
     for mx, want in ((1.0, 4096.0), (1.0 + 2.0 ** -13, 4096.0), (3.0, 2048.0), (0.99, 8192.0), (0.0, 1.0), (np.inf, 1.0), (4096.0, 1.0), (8191.0, 1.0)):
-        assert gen.pick_scale(mx) == want
+        assert f16s.pick_scale(mx) == want
         if 0 < mx < np.inf:
-            assert 4096.0 <= mx * gen.pick_scale(mx) < 8192.0
+            assert 4096.0 <= mx * f16s.pick_scale(mx) < 8192.0
 
 
 @pytest.mark.parametrize("S", [11, 15])
@@ -79,6 +80,10 @@ def test_stone_planes_hold_the_special_boards(S):
     assert (singles.sum(axis=(1, 2, 3)) == 1).all()
     for (yy, xx) in ((0, 0), (0, S - 1), (S - 1, 0), (S - 1, S - 1), (0, m), (m, 0), (S - 1, m), (m, S - 1), (m, m)):
         assert (singles[:, :, yy, xx].sum(axis=0) == 1).all()
+    # the bytes the function produced before it grew to max(S*S, 32) positions for boards below 6x6 (sha256 of the float64 array)
+    import hashlib
+    assert hashlib.sha256(x.tobytes()).hexdigest() == {11: "8a3cb13d605e51fd85991330f03942892e3b4f53e98489166d0990da03edd63f",
+                                                       15: "8e576f0b21765ad3a4b824cf76aaafd2613937472ad6da6d16bc6fc31079a314"}[S]
 
 
 def _check_exact_case(S, target, cls):
@@ -89,11 +94,11 @@ def _check_exact_case(S, target, cls):
     assert key == key2
     # every weight, after its group's scale, is hi + lo exactly
     wlo = {}
-    scales = gen.scale_groups(v)
+    scales = f16s.scale_groups(v)
     for name, s in scales.items():
         w32 = v[name].astype(np.float32)
         assert (w32 == v[name]).all(), name
-        hi, lo = gen.split16(w32 * np.float32(s))
+        hi, lo = f16s.split16(w32 * np.float32(s))
         assert (hi + lo == v[name] * s).all(), name
         assert np.abs(hi).max() < 8192.0
         wlo[name] = bool((lo != 0).any())
@@ -108,7 +113,7 @@ def _check_exact_case(S, target, cls):
         a = out[k]
         a32 = a.astype(np.float32)
         assert (a32 == a).all(), k
-        hi, lo = gen.split16(a32)
+        hi, lo = f16s.split16(a32)
         assert (hi + lo == a).all(), k
         assert a.min() >= 0.0 and a.max() <= 2048.0, (k, a.min(), a.max())
         if cls == "int":
@@ -132,7 +137,7 @@ def _check_exact_case(S, target, cls):
         assert wlo[kname] and not xlo[tin] and _integral(out["pre:" + key], 13) and not _integral(out["pre:" + key], 12)
     if cls == "xsplit":
         assert xlo[tin] and not wlo[kname] and _integral(out["pre:" + key], 12) and not _integral(out["pre:" + key], 11)
-        assert (gen.split16(out[tin].astype(np.float32))[1] != 0).all()                  # a lo half at every site
+        assert (f16s.split16(out[tin].astype(np.float32))[1] != 0).all()                  # a lo half at every site
     if target not in ("stem", "vconv", "pconv"):
         assert (v[kname] != 0).any(axis=(0, 1, 3)).all() and (v[kname] != 0).any(axis=(2, 3)).all()      # every cin, every tap
     return v, planes, key, out, tin
@@ -158,10 +163,10 @@ def test_exact_generators_meet_the_exactness_conditions_11(target, cls):
         assert (leak != 0).any()
     # one lo half dropped
     if cls == "wsplit":
-        s = gen.scale_groups(v)[kname]
-        assert (net_fp64._conv2d_flat(x, gen.split16((k * s).astype(np.float32))[0] / s, zero) != good).any()
+        s = f16s.scale_groups(v)[kname]
+        assert (net_fp64._conv2d_flat(x, f16s.split16((k * s).astype(np.float32))[0] / s, zero) != good).any()
     if cls == "xsplit":
-        assert (net_fp64._conv2d_flat(gen.split16(x.astype(np.float32))[0], k, zero) != good).any()
+        assert (net_fp64._conv2d_flat(f16s.split16(x.astype(np.float32))[0], k, zero) != good).any()
 
 
 @pytest.mark.parametrize("target,cls", gen.CASES)
@@ -196,9 +201,9 @@ def test_rounded_weights_span_twelve_binades_and_both_signs():
         assert np.abs(out[key]).max() < 65504.0
 
 
-@pytest.mark.parametrize("side,where", gen.ENVELOPE)
+@pytest.mark.parametrize("side,where", f16s.ENVELOPE)
 def test_envelope_cases_lie_in_the_binades_they_claim(side, where):
-    v, x, key = gen.envelope_variables(side, where)
+    v, x, key = f16s.envelope_variables(side, where)
     out = net_fp64.intermediates(v, x)
     top = np.abs(out[key]).max()
     if side == "large":
@@ -212,7 +217,7 @@ def test_envelope_cases_lie_in_the_binades_they_claim(side, where):
 def test_shipped_checkpoint_keeps_its_headroom():
     """Largest |activation| per stage of the shipped checkpoint on the 64 positions of board_positions(11, 64, seed=0): 174x below
     fp16's maximum.  A retrained fixture that fails this is a finding, not a tolerance to widen."""
-    with np.load(gen.W6960) as z:
+    with np.load(f16s.W6960) as z:
         v = {k: z[k] for k in z.files}
     out = net_fp64.intermediates(v, gen.board_positions(11, 64, seed=0))
     stage = {"stem": ("f0",), "bone/block1": ("g1", "o1"), "bone/block2": ("g2", "o2"), "value/block3": ("g3", "o3"),

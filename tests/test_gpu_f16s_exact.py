@@ -1,5 +1,6 @@
 """The fp16 split-operand forward (csrc/af_conv_f16s.hip, conv path 5 on 11x11 and 15x15) against oracle/net_fp64.intermediates, one
-layer at a time, through the per-layer read-back HipNet.debug_activation (af_net_debug_activation).
+layer at a time, through the per-layer read-back HipNet.debug_activation (af_net_debug_activation).  The generators of the cases
+are generic in the board size and live in tests/net_cases.py.
 
 EXACT REGIME.  One layer (the TARGET: the stem, conv1 / conv2 / the 1x1 projection of one of the five blocks, a head convolution)
 carries random weights; every other layer is a centre-tap SELECTOR (cout c takes cin (c + 5 (c // Cin)) mod Cin where the net
@@ -71,28 +72,15 @@ No case drives an activation past 65504: beyond it the outputs are undefined (in
 """
 import functools
 import os
-import zlib
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from net_cases import BLOCKS, CASES, LAYERS, board_positions, dense_case, exact_reference, exact_variables, rounded_variables
 from oracle import net_fp64
 
 W6960 = os.path.join(GOLDEN, "alphaFive-6960.weights.npz")
-# (name, cin, cout, key of the block's input)
-BLOCKS = (("bone/block1", 32, 64, "f0"), ("bone/block2", 64, 128, "o1"), ("value/block3", 128, 32, "o2"),
-          ("policy/block4", 128, 64, "o2"), ("policy/block5", 64, 32, "o4"))
-STORED = ("f0", "g1", "o1", "g2", "o2", "g3", "o3", "g4", "o4", "g5", "o5", "vconv", "pconv")      # every activation the kernels split
-TARGETS = ("stem",) + tuple("b%d.%s" % (k, part) for k in range(1, 6) for part in ("conv1", "conv2", "proj")) + ("vconv", "pconv")
-CLASSES = ("int", "wsplit", "xsplit")
-CASES = tuple((t, c) for t in TARGETS for c in CLASSES if not (t == "stem" and c == "xsplit"))     # (the stem's input is the planes)
-Q = {"int": 0, "wsplit": 13, "xsplit": 12}      # every product of a case is a multiple of 2^-Q
-# the convolutions in graph order: (output key, variable prefix, projection prefix joined to the sum, input key, projection's input key)
-LAYERS = (("f0", "bone/conv1", None, "planes", None),) + tuple(
-    lay for k, (name, _, _, src) in enumerate(BLOCKS, 1)
-    for lay in (("g%d" % k, name + "_conv1", None, src, None), ("o%d" % k, name + "_conv2", name + "_res", "g%d" % k, src))
-) + (("vconv", "value/conv", None, "o3", None), ("pconv", "policy/conv", None, "o5", None))
 # scale groups of the packer (f16s_update_absmax): kernels that share one power-of-two scale
 FOLDED = (1, 2, 4)                               # blocks whose projection rides conv2 as extra k-steps; 3 and 5 produce it separately
 CONFIGS11 = ((1, 0), (2, 0), (8, 0), (9, 0), (121, 0), (1025, 0), (8, 256), (9, 256), (8, 2048), (9, 16), (121, 32), (8, 128))
@@ -144,182 +132,7 @@ def scale_groups(v):
     return out
 
 
-# ------------------------------------------------------------------ generators (numpy, no GPU) ------------------------------------------------------------------
-def _sel3(cin, cout):
-    k = np.zeros((3, 3, cin, cout))
-    c = np.arange(cout)
-    k[1, 1, c if cout <= cin else (c + 5 * (c // cin)) % cin, c] = 1.0
-    return k
-
-
-def base_variables(S):
-    """All 42 variables (float64, TF layout) of the selector network: nothing but copies of the planes, dense layers zero."""
-    n = S * S
-    v = {"bone/conv1/kernel": np.zeros((5, 5, 3, 32)), "bone/conv1/bias": np.zeros(32)}
-    c = np.arange(32)
-    v["bone/conv1/kernel"][2, 2, c % 3, c] = 1.0 + (c // 3) % 3
-    for name, cin, cout, _ in BLOCKS:
-        v[name + "_conv1/kernel"], v[name + "_conv1/bias"] = _sel3(cin, cout), np.zeros(cout)
-        v[name + "_conv2/kernel"], v[name + "_conv2/bias"] = _sel3(cout, cout), np.zeros(cout)
-        v[name + "_res/kernel"], v[name + "_res/bias"] = np.zeros((1, 1, cin, cout)), np.zeros(cout)
-    for head, nc in (("value", 4), ("policy", 16)):
-        v[head + "/conv/kernel"], v[head + "/conv/bias"] = np.zeros((1, 1, 32, nc)), np.zeros(nc)
-        v[head + "/conv/kernel"][0, 0, np.arange(nc), np.arange(nc)] = 1.0
-    v["value/fc1/kernel"], v["value/fc1/bias"] = np.zeros((4 * n, 64)), np.zeros(64)
-    v["value/fc2/kernel"], v["value/fc2/bias"] = np.zeros((64, 1)), np.zeros(1)
-    v["policy/fc/kernel"], v["policy/fc/bias"] = np.zeros((16 * n, n)), np.zeros(n)
-    return v
-
-
-def fold_head(v, head):
-    """The value / policy head convolution as a fold of all 32 channels of o3 / o5 (which are never stored); exact_variables sets its bias."""
-    nc = 4 if head == "value" else 16
-    k = np.zeros((1, 1, 32, nc))
-    for ci in range(32):
-        k[0, 0, ci, ci % nc] = (-1.0) ** (ci // nc)
-    v[head + "/conv/kernel"], v[head + "/conv/bias"] = k, np.zeros(nc)
-
-
-def site_planes(S):
-    """[S*S, 3, S, S] of 0 / 1: position b holds one stone per plane p, at pixel (37 p + b) mod S*S."""
-    n = S * S
-    x = np.zeros((n, 3, n))
-    for p in range(3):
-        x[np.arange(n), p, (37 * p + np.arange(n)) % n] = 1.0
-    return x.reshape(n, 3, S, S)
-
-
-def stone_planes(S, rng):
-    """[S*S, 3, S, S] of 0 / 1: a full board, an empty one, single stones in every plane at the four corners, the four edge
-    midpoints and the centre, then random fill of rising density."""
-    n, m = S * S, S // 2
-    x = np.zeros((n, 3, S, S))
-    x[0] = 1.0
-    k = 2
-    for (yy, xx) in ((0, 0), (0, S - 1), (S - 1, 0), (S - 1, S - 1), (0, m), (m, 0), (S - 1, m), (m, S - 1), (m, m)):
-        for c in range(3):
-            x[k, c, yy, xx] = 1.0
-            k += 1
-    for b in range(k, n):
-        x[b] = rng.random((3, S, S)) < (0.1 + 0.8 * (b - k) / (n - k))
-    return x
-
-
-def target_names(target):
-    """-> (kernel variable, bias variables that sum to its bias, output key, the variable whose bias produces its input)."""
-    if target == "stem":
-        return "bone/conv1/kernel", ("bone/conv1/bias",), "f0", None
-    producer = {"f0": "bone/conv1/bias", "o1": "bone/block1_conv2/bias", "o2": "bone/block2_conv2/bias", "o4": "policy/block4_conv2/bias"}
-    if target in ("vconv", "pconv"):
-        head, blk = ("value", "value/block3") if target == "vconv" else ("policy", "policy/block5")
-        return head + "/conv/kernel", (head + "/conv/bias",), target, blk + "_conv2/bias"
-    k, part = int(target[1]), target[3:]
-    name, _, _, src = BLOCKS[k - 1]
-    if part == "conv1":
-        return name + "_conv1/kernel", (name + "_conv1/bias",), "g%d" % k, producer[src]
-    if part == "conv2":
-        return name + "_conv2/kernel", (name + "_conv2/bias", name + "_res/bias"), "o%d" % k, name + "_conv1/bias"
-    return name + "_res/kernel", (name + "_conv2/bias", name + "_res/bias"), "o%d" % k, producer[src]
-
-
-@functools.lru_cache(maxsize=4)
-def exact_variables(S, target, cls):
-    """-> (variables, planes [S*S, 3, S, S], output key of the target) of one exact case."""
-    rng = np.random.default_rng(zlib.crc32(("%d %s %s" % (S, target, cls)).encode()))
-    v = base_variables(S)
-    planes = stone_planes(S, rng) if target == "stem" else site_planes(S)
-    kname, bnames, key, producer = target_names(target)
-    folded = target[0] == "b" and target[1] in "35"
-    if folded:
-        fold_head(v, "value" if target[1] == "3" else "policy")
-    if target.endswith("proj"):
-        v[kname.replace("_res/", "_conv2/")][:] = 0.0
-    if cls == "xsplit":
-        nb = v[producer].shape[0]
-        v[producer] = 1.0 + (1.0 + np.arange(nb) % 3) * 2.0 ** -12
-    shape = v[kname].shape
-    w = rng.integers(-1, 2, size=shape) * (rng.random(shape) < 0.75)
-    if cls == "wsplit":
-        w = w * (1.0 + 2.0 ** -13 * rng.integers(0, 2, size=shape))
-    v[kname] = w.astype(np.float64)
-    # integer biases, distinct per cout, above the most negative sum of the case: every stored activation stays on the ELU's x >= 0 side
-    pre = net_fp64.intermediates(v, planes, flat=True)["pre:" + key]
-    cout = shape[-1]
-    total = np.ceil(max(0.0, -pre.min())) + 1.0 + rng.permutation(cout)
-    if folded:                                                   # the fold's bias keeps the head convolution on the x >= 0 side as well
-        head = "value" if target[1] == "3" else "policy"
-        o = pre + total[None, :, None, None]                     # = o3 / o5: everything behind the target is a selector
-        fold = np.einsum("bchw,cd->bdhw", o, v[head + "/conv/kernel"][0, 0])
-        v[head + "/conv/bias"] = np.full(fold.shape[1], np.ceil(max(0.0, -fold.min())) + 1.0)
-    if len(bnames) == 2:                                         # the kernels see only conv2 bias + projection bias
-        v[bnames[1]] = 1.0 + rng.permutation(cout) % 7
-        total = total - v[bnames[1]]
-    v[bnames[0]] = v[bnames[0]] + total
-    return v, planes, key
-
-
-@functools.lru_cache(maxsize=2)
-def exact_reference(S, target, cls):
-    """-> {key: float32 [S*S, C, S*S]} of every stored activation of the case; the conversion from fp64 is checked to be exact."""
-    v, planes, _ = exact_variables(S, target, cls)
-    ref = net_fp64.intermediates(v, planes, flat=True)
-    out = {}
-    for key in STORED:
-        a32 = ref[key].astype(np.float32)
-        assert (a32.astype(np.float64) == ref[key]).all(), key
-        out[key] = a32.reshape(a32.shape[0], a32.shape[1], -1)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def dense_case(S):
-    """Selector dense layers on 0 / 1 boards: logit j = pconv[j mod 16, pixel j] + (j mod 3) with pconv[c] = 1 + 2 o5[c] in {1, 3, 5, 7};
-    x = sum of eight vconv values, four with weight +1 and four with -1 (vconv[c] = o3[c] in {0, 1, 2}): an integer in [-8, 8]."""
-    n = S * S
-    rng = np.random.default_rng(40 + S)
-    v = base_variables(S)
-    v["policy/conv/kernel"] *= 2.0
-    v["policy/conv/bias"] += 1.0
-    j = np.arange(n)
-    v["policy/fc/kernel"][(j % 16) * n + j, j] = 1.0
-    v["policy/fc/bias"] = (j % 3).astype(np.float64)
-    pix = rng.permutation(n)[:8]
-    for i in range(8):
-        v["value/fc1/kernel"][(i % 4) * n + pix[i], i] = 1.0
-        v["value/fc2/kernel"][i, 0] = 1.0 if i < 4 else -1.0
-    planes = (rng.random((64, 3, S, S)) < 0.5).astype(np.float64)
-    ref = net_fp64.intermediates(v, planes)
-    return v, planes, ref
-
-
-# ---- rounded regime ----
-def rounded_variables(S, seed):
-    """Glorot kernels, biases of order 1, and bone/block2 conv1's members spread over 2^12 in magnitude (float32 values)."""
-    from alphafive_amd.network import random_variables
-    rng = np.random.default_rng(seed)
-    v = random_variables(S, seed=seed)
-    for name in v:
-        if name.endswith("bias"):
-            v[name] = (0.75 * rng.standard_normal(v[name].shape)).astype(np.float32)
-    k = v["bone/block2_conv1/kernel"]
-    v["bone/block2_conv1/kernel"] = (k * 2.0 ** -rng.integers(0, 13, size=k.shape)).astype(np.float32)
-    return v
-
-
-def board_positions(S, B, seed=0):
-    """The 0 / 1 boards of tests/test_gpu_net.py::_positions."""
-    rng = np.random.RandomState(seed)
-    x = np.zeros((B, 3, S, S), np.float32)
-    for b in range(B):
-        n = rng.randint(0, S * S - 1)
-        cells = rng.permutation(S * S)[:n + 1]
-        x[b, 0].reshape(-1)[cells[0:n:2]] = 1
-        x[b, 1].reshape(-1)[cells[1:n:2]] = 1
-        if b % 7:
-            x[b, 2].reshape(-1)[cells[n]] = 1
-    return x
-
-
+# ---- rounded regime (the generators of the cases, generic in the board size: tests/net_cases.py) ----
 ENVELOPE = (("large", "trunk"), ("large", "branch"), ("small", "trunk"), ("small", "branch"))
 ENVELOPE_LAYER = {"trunk": ("bone/block2", "g2"), "branch": ("policy/block4", "g4")}
 
