@@ -19,7 +19,7 @@ HIPCC_FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-shared"
 TARGETS = {
     "libaf_hip.so": (["csrc/af_engine.hip"], ["-ffp-contract=off"]),
     "libaf_net.so": (["csrc/af_net.hip", "csrc/af_conv_f16s.hip"], []),
-    "libaf_tower.so": (["csrc/af_tower_bf16.hip"], []),
+    "libaf_tower.so": (["csrc/af_tower_bf16.hip", "csrc/af_tower_i8.hip"], []),
     "libaf_replay.so": (["csrc/af_replay.hip"], []),
     # the trainer's Adam is held to a numpy specification bit for bit (train_hip.adam_reference): as written, too
     "libaf_train.so": (["csrc/af_train.hip"], ["-ffp-contract=off"]),

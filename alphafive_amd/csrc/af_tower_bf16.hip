@@ -31,6 +31,9 @@
 // Roofline: 2*128*128*9*121 = 35.7 MFLOP per position and convolution on 2.5 PFLOP/s dense bf16 MFMA;
 // per position a workgroup reads 36 KB (+36 KB PROJ) and writes 31 KB of HBM: 8192 positions x 16 convolutions
 // = 4.7 TFLOP and ~11 GB per tower pass, i.e. MFMA-bound (1.9 ms) over HBM (1.4 ms at 8 TB/s) by a small margin.
+//
+// The handle struct and the device helpers the int8 residual blocks (af_tower_i8.hip) share with this file — LDS-DMA, elu1, the
+// first position of a persistent workgroup, Geo<S>, pack_perm — are in af_tower_common.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -38,17 +41,11 @@
 
 #include <vector>
 
-#include "af_tower_bf16.h"
+#include "af_tower_common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define TW_HIP_OK(expr)                                      \
-    do {                                                     \
-        hipError_t err_ = (expr);                            \
-        if (err_ != hipSuccess) return AF_TOWER_ERR_HIP;     \
-    } while (0)
 
 // (r3 A/B record, profiles/r3_18_tower_ab.txt; both were build-time switches until nothing built them any other way: the nt hint on
 //  the LDS-DMA loads: 5.29 -> 5.17 ms per 8192-position tower pass; lanes past the board read zeros: within noise, 5.16-5.17 with both)
@@ -57,21 +54,8 @@ constexpr int kVSlack = 88;      // architectural VGPRs left to everything that 
 #define AF_TOWER_ABL_NOLDS 0     // profiling build: af_tower_conv without its B-fragment reads (results wrong by design)
 #endif
 
-// LDS-DMA: 16 bytes per lane from global memory into LDS at (wave-uniform lds_dst) + lane*16; counted on vmcnt.
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// ELU as max(x, min(exp(x), 1) - 1): x > 0 ? x : exp(x) - 1 with one v_max_f32 instead of compare + select and the clamp riding on
-// v_exp_f32 (r3_44).  exp(x) - 1 > x for x < 0 and the clamped exponential is exactly 1 for x >= 0; only for -3e-4 < x < 0 can the
-// rounding of v_exp_f32 put exp(x) - 1 below x, and the max then returns x, within 5e-8 of the true value (see af_conv_f16s.hip)
-__device__ __forceinline__ float elu1(float x) {
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    return fmaxf(x, fminf(fmaxf(e, 0.0f), 1.0f) - 1.0f);
-}
-// ... and two at a time on 2-vectors, which keeps the bias add in front and the "- 1" as v_pk_add_f32 (hipcc's SLP vectoriser pairs them
+// (glds16, the LDS-DMA, and elu1, the ELU as max(x, min(exp(x), 1) - 1): af_tower_common.h)
+// elu1 two at a time on 2-vectors, which keeps the bias add in front and the "- 1" as v_pk_add_f32 (hipcc's SLP vectoriser pairs them
 // in the compare / select form but not in the max form): 3 + v_exp_f32 instead of 4 + v_exp_f32 issue slots per element
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 elu2(f32x2 x) {
@@ -81,14 +65,6 @@ __device__ __forceinline__ f32x2 elu2(f32x2 x) {
     e.y = fminf(fmaxf(__builtin_amdgcn_exp2f(t.y), 0.0f), 1.0f);
     const f32x2 em1 = e - 1.0f;
     return f32x2{fmaxf(x.x, em1.x), fmaxf(x.y, em1.y)};
-}
-
-// First position of a persistent workgroup (r4, as in af_conv_f16s.hip): consecutive workgroup ids sit on consecutive XCDs, so with
-// pos = blockIdx.x the 32 workgroups of XCD k would walk the positions = k (mod 8) only; XCD k takes the contiguous positions
-// 32k..32k+31 (+ gridDim.x per pass) instead.  A position's result does not depend on the workgroup that computes it.
-__device__ __forceinline__ int first_position() {
-    if ((gridDim.x & 7) == 0) return (int)(blockIdx.x >> 3) + (int)(gridDim.x >> 3) * (int)(blockIdx.x & 7);
-    return (int)blockIdx.x;
 }
 
 struct TowerArgs {
@@ -102,37 +78,7 @@ struct TowerArgs {
     char* dump;          // af_tower_conv3: 4 KB the lanes past the board store to (an unconditional store keeps the epilogue out of a branch)
 };
 
-// Board geometry: every size below is a compile-time member of Geo<S> (as in af_conv_f16s.hip); the host forks once, in with_geo.
-//   11x11: a position is one unit of work.  Its plane is 13 rows x 11 pixels (+1) = 144 units per channel octet, pixel n at unit
-//          n + 11, and goes to LDS as it lies in memory: 9 LDS-DMA rounds of 256 lanes x 16 B.
-//   15x15: 225 pixels are 8 pixel tiles and a 64-KB plane — neither the four accumulator sets nor three planes in LDS hold a whole
-//          position — so the convolution runs every board as HALVES = 2 pseudo-positions: half 0 computes board rows 0..7 (120
-//          pixels), half 1 rows 8..14 (105).  A half stages its rows plus one above and one below: 10 rows = 150 units per octet
-//          from unit 120 * half of the 256-unit plane (half 1: the 135 units up to the plane's last row, the bottom zero row), gathered
-//          by the per-lane addresses of the LDS-DMA into one contiguous half-plane of LPIX = 160 units per octet (a kg stride that
-//          is a multiple of 128 B, as 144 is): 10 rounds.  Inside a half-plane pixel n of the half sits at unit n + 15, exactly as
-//          pixel n sits at unit n + 11 above, so the tap addresses are the same expressions.
-//          Stem, heads and dense layers work on whole positions: 8 pixel / output tiles.
-constexpr uint32_t kLds0 = 256u;                                        // planes start here: unit -1 of a plane stays inside LDS
-template <int S_> struct Geo;
-template <> struct Geo<11> {
-    static constexpr int S = 11, NPIX = 121, HALVES = 1;
-    static constexpr int PIX = 144, LPIX = 144;                         // units per channel octet: in memory, in LDS
-    static constexpr int HPIX0 = 121, HPIX1 = 121, HOFF = 0;            // pixels of half 0 / 1; plane unit where half 1 starts
-    static constexpr int LIVE0 = 144, LIVE1 = 144;                      // units per octet a half stages
-    static constexpr uint32_t kZeroB = 33024u;                          // all-zero LDS region the edge lanes read instead of a wrapped neighbour
-    static constexpr int NT = 4;                                        // 32-pixel tiles of a whole position (= 32-output tiles of the policy)
-    static constexpr int KP = 121, KV = 31, KVPAD = 496;                // k-steps of the policy / value-fc1 dense layers
-};
-template <> struct Geo<15> {
-    static constexpr int S = 15, NPIX = 225, HALVES = 2;
-    static constexpr int PIX = 256, LPIX = 160;
-    static constexpr int HPIX0 = 120, HPIX1 = 105, HOFF = 120;
-    static constexpr int LIVE0 = 150, LIVE1 = 135;
-    static constexpr uint32_t kZeroB = (14u * 160u + 2u * 15u + 2u) * 16u + 272u;    // 36,624: the largest tap offset + a lane's bank offset + one unit
-    static constexpr int NT = 8;
-    static constexpr int KP = 225, KV = 57, KVPAD = 912;
-};
+// Board geometry Geo<S> — 11x11 whole positions, 15x15 as two half boards — and kLds0: af_tower_common.h.
 template <class G> struct Lay {
     static constexpr uint32_t kPlaneB = 16u * G::PIX * 16u;             // bytes per position in memory: 36,864 / 65,536
     static constexpr uint32_t kPlaneL = 16u * G::LPIX * 16u;            // bytes per (half-)plane in LDS: 36,864 / 40,960
@@ -1110,7 +1056,7 @@ __device__ __forceinline__ uint32_t pack_bf16(float f) {
     return u >> 16;
 }
 __device__ __forceinline__ float pack_bf16_f32(float f) { return __uint_as_float(pack_bf16(f) << 16); }
-__device__ __forceinline__ int pack_perm(int m) { return 16 * ((m >> 2) & 1) + 8 * (m >> 4) + 4 * ((m >> 3) & 1) + (m & 3); }   // MFMA row -> output: a lane's 16 accumulator rows are 16 consecutive outputs
+// (pack_perm, MFMA row -> output, so that a lane's 16 accumulator rows are 16 consecutive outputs: af_tower_common.h)
 __device__ __forceinline__ uint4 pack_row(const uint32_t (&h)[8]) {
     return uint4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
 }
@@ -1260,13 +1206,7 @@ __global__ __launch_bounds__(256) void af_tower_pack_ends_kernel(PackEndsArgs A)
 enum { kW1, kW2, kB1, kB2 };        // w1 / w2: A fragments of a block's two convolutions [wave][s][lane][e], s = 8 tap + cin / 16, then the 1x1 projection
 enum { kStemW, kStemB, kHeadsW, kHeadsB, kHeadsA, kHeadsB32, kDenseWp, kDenseWv, kDensePb, kDenseVb1, kDenseVw2, kDenseVb2, kEnds };
 
-// What the host needs of a geometry, as plain numbers: filled once, in af_tower_create, from Geo<S> (dims_of).
-struct Dims {
-    int S, npix, pix;               // board side, pixels, units per channel octet of the C8 layout
-    int halves;                     // pseudo-positions per board of a convolution launch
-    int rows_wp, rows_wv, pb_words; // the dense regions of the ends packer
-    int ends_threads;
-};
+// Dims, what the host needs of a geometry as plain numbers, filled once in af_tower_create from Geo<S> (dims_of): af_tower_common.h.
 template <class G> static Dims dims_of() {
     return Dims{G::S, G::NPIX, G::PIX, G::HALVES, Ends<G>::kRowsWp, Ends<G>::kRowsWv, Ends<G>::kPbWords, Ends<G>::kThreads};
 }
@@ -1306,18 +1246,7 @@ static int64_t stage_floats(const Dims& d) {
 }
 constexpr int64_t kDumpBytes = 4096;                                // TowerArgs::dump
 
-struct af_tower {
-    int S = 0, width = 0, blocks = 0, device = 0;
-    Dims d = {};
-    int ncu = 0;                    // compute units of `device`: the persistent grid of a convolution launch
-    char* arena = nullptr;          // the one allocation: every buffer of the table, the staging area and dump, at 256-byte offsets
-    std::vector<char*> buf;         // 4 * blocks + 12 buffers; their addresses never change
-    std::vector<char> set;          // per group: its host setter has run
-    float* stage = nullptr;         // where a host setter's fp32 arrays wait for the packers
-    char* dump = nullptr;
-    template <class T> T* block(int b, int k) const { return reinterpret_cast<T*>(buf[4 * b + k]); }
-    template <class T> T* end(int k) const { return reinterpret_cast<T*>(buf[4 * blocks + k]); }
-};
+// (struct af_tower, the handle: af_tower_common.h)
 
 // The one fork between the geometries: f(Geo<11>{}) or f(Geo<15>{}) (af_tower_create admits no other size).
 template <class F>
@@ -1337,6 +1266,7 @@ static void pack_blocks(const af_tower* t, hipStream_t st, int b0, int nb, const
         a.b1[j] = t->block<float>(b0 + j, kB1); a.b2[j] = t->block<float>(b0 + j, kB2);
     }
     hipLaunchKernelGGL(af_tower_pack_blocks_kernel, dim3(kPackBlockThreads / 256, nb), dim3(256), 0, st, a);
+    if (t->i8) af_tower_i8_pack(t, st, b0, nb, src);             // an int8-enabled handle: its packers follow, from the same sources
 }
 
 // range [first, end) of the ends kernel from src: stem_w, stem_b, then the ten device tensors behind the blocks in
@@ -1386,6 +1316,7 @@ static int packed(af_tower* t, int group) {
 static int g_depth = 0;     // B-fragment ring depth (A/B knob; 0 = per-kernel default)
 static int g_abl = 0;       // profiling ablations (results wrong by design)
 static int g_grid = 0;      // persistent workgroups (0 = one per CU)
+int af_tower_grid_override() { return g_grid; }
 static int g_heads = 1;     // heads' 1x1 convolutions: 1 = af_tower_heads_mfma_kernel (r4), 0 = the VALU kernel (A/B)
 static int g_engine = 3;    // 3 (default, r4): af_tower_conv3 for a block's first convolution + af_tower_conv for its second (bit-identical to 0,
                             //    4.143 vs 4.167 ms per 8192-position tower pass); 0: af_tower_conv for both; 2: af_tower_conv3 for both (its
@@ -1487,13 +1418,14 @@ static int allocate(af_tower* t) {
     const int n = 4 * t->blocks + kEnds;
     auto padded = [](int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); };
     const int64_t stage_bytes = stage_floats(t->d) * 4;
-    size_t total = padded(stage_bytes) + padded(kDumpBytes);
+    size_t total = padded(stage_bytes) + padded(kDumpBytes) + af_tower_i8_arena_bytes(t);
     for (int i = 0; i < n; ++i) total += padded(buffer_bytes(i, t->blocks, t->d));
     { void* q = nullptr; TW_HIP_OK(hipMalloc(&q, total)); t->arena = static_cast<char*>(q); }
     char* p = t->arena;
     for (int i = 0; i < n; ++i) { t->buf.push_back(p); p += padded(buffer_bytes(i, t->blocks, t->d)); }
     t->stage = reinterpret_cast<float*>(p); p += padded(stage_bytes);
-    t->dump = p;
+    t->dump = p; p += padded(kDumpBytes);
+    { const int rc = af_tower_i8_carve(t, p); if (rc) return rc; }   // the int8 path's buffers: the rest of the allocation
     t->set.assign(t->blocks + kEndGroups, 0);
     // dense_pb's words behind the last pixel (121..127 / 225..255) — policy outputs that do not exist — are -1e30 for good: no packer writes them
     const std::vector<float> tail(t->d.pb_words - t->d.npix, -1.0e30f);

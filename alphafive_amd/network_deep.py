@@ -33,7 +33,8 @@ def variable_shapes(board_size, blocks=8, width=128):
 
 
 class _HipEvaluator(object):
-    """planes -> (prob, value) on the hand-written kernels; bind_outputs lets the engine own the result tensors.  An evaluator
+    """planes -> (prob, value) on the hand-written kernels (the tower's precision, bf16 or int8, picks the blocks' kernels in
+    eval_hip); bind_outputs lets the engine own the result tensors.  An evaluator
     owns its tower — handle, packed weights, activation buffers, bound outputs — so every consumer of a net (a Player, a self-play
     engine, an arena) has one of its own; the net re-packs all of them when its weights change (DeepResNet._towers)."""
 
@@ -211,25 +212,37 @@ class DeepResNet(object):
         return p, v
 
     # ---- hand-written tower (csrc/af_tower_bf16.hip) ----
-    def select_backend(self, name, max_batch):
-        """"hip": torch stem -> af_tower_forward -> torch heads (raises if libaf_tower.so is missing);
+    def select_backend(self, name, max_batch, precision="bf16", act_scales=None):
+        """"hip": the whole forward on the hand-written kernels (raises if libaf_tower.so is missing), the residual blocks in
+        `precision` — "bf16" (default: today's kernels and bits) or "int8" with act_scales (see evaluator);
         "torch": the all-PyTorch path."""
         if name == "torch":
             return self.eval_device
         if name != "hip":
             raise ValueError(name)
+        ev = self.evaluator(max_batch, precision=precision, act_scales=act_scales)   # the net's primary evaluator: its tower is what eval_hip(x) runs on
         self._pack_version = getattr(self, "_pack_version", 0) + 1
-        ev = self.evaluator(max_batch)           # the net's primary evaluator: its tower is what eval_hip(x) runs on
         self._tower = ev.tower
         return ev
 
-    def evaluator(self, max_batch):
+    def evaluator(self, max_batch, precision="bf16", act_scales=None):
         """A new evaluator with a tower of its own, packed from the net's current tensors: one per consumer, so that two Players,
         or a Player and a self-play engine, share the net and not each other's buffers.  It follows set_variables /
-        set_variables_device / load_npz in place until its close() (or the net's)."""
-        from . import tower_hip
+        set_variables_device / load_npz in place until its close() (or the net's).
+
+        precision="int8" (11x11 nets): the residual blocks run with int8 weights and int8 stored activations
+        (csrc/af_tower_i8.hip, specified by alphafive_amd/tower_i8.py); stem, heads and dense layers stay bf16.  act_scales are
+        the 2 * blocks activation scales of calibrate_int8.  An int8 evaluator runs the persistent kernels at every batch — there
+        is no int8 small-batch form — so a position's bits do not depend on the batch it is evaluated in.  Weight updates
+        re-quantise the weights in place like the bf16 ones; the ACTIVATION scales stay as calibrated until the caller calibrates
+        again (calibrate_int8 on the new weights, then evaluator.tower.enable_i8(scales))."""
+        from . import tower_hip, tower_i8
+        tower_hip.check_precision(precision, self.board_size, act_scales)
+        if precision == "int8":
+            act_scales = tower_i8.check_scales(act_scales, self.blocks)
         tower = tower_hip.HipTower(self.tower, self.board_size, self.width, max_batch, self.device, stem=self.stem,
-                                   vconv=self.vconv, pconv=self.pconv, dense=self.vfc1 + self.vfc2 + self.pfc)
+                                   vconv=self.vconv, pconv=self.pconv, dense=self.vfc1 + self.vfc2 + self.pfc,
+                                   precision=precision, act_scales=act_scales)
         ev = _HipEvaluator(self, tower)
         self._evaluators.add(ev)
         return ev
@@ -243,12 +256,33 @@ class DeepResNet(object):
         tw = self._tower if tower is None else tower
         B = x.shape[0]
         tw.stem(x.contiguous())
-        if B <= tw.small_batch:
+        if tw.precision == "int8":
+            tw.forward_i8(B)                     # the persistent int8 kernels at every batch: no int8 small-batch form
+        elif B <= tw.small_batch:
             tw.forward_small(B)
         else:
             tw.forward(B)
         tw.heads(B)
         return tw.dense(B)
+
+    @torch.no_grad()
+    def calibrate_int8(self, planes, margin=1.0):
+        """Activation scales for precision="int8": the fp32 torch path (eval_device's arithmetic, the net's weights in fp32) layer
+        by layer over the caller's positions — planes float32 [B,3,S,S], array or tensor — on PyTorch ops only, no hand-written
+        kernel.  -> float32 [2 * blocks] in tower_i8's order h_0, g_0, h_1, g_1, ...: fp32(absmax * margin / 127) of every
+        block's input and mid activation over all positions (a tensor that is zero everywhere gets scale 1).  Deterministic."""
+        x = planes if torch.is_tensor(planes) else torch.from_numpy(np.ascontiguousarray(planes, np.float32))
+        c = (lambda wb: (wb[0].float(), wb[1].float()))
+        h = F.elu(F.conv2d(x.to(self.device, torch.float32), *c(self.stem), padding=2))
+        out = []
+        for blk in self.tower:
+            g = F.elu(F.conv2d(h, *c(blk["c1"]), padding=1))
+            out += [h.abs().max(), g.abs().max()]
+            h = F.elu(F.conv2d(h, *c(blk["res"])) + F.conv2d(g, *c(blk["c2"]), padding=1))
+        amax = torch.stack(out).double().cpu().numpy()
+        scales = (amax * float(margin) / 127.0).astype(np.float32)
+        scales[scales == 0] = 1.0
+        return scales
 
     def eval(self, inputs):
         """network.py:90-97, as ResNet.eval: numpy float32[B,3,S,S] -> (prob[B,S*S], value[B]) numpy.  A cuda net evaluates on the

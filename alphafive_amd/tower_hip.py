@@ -51,6 +51,15 @@ def lib():
         L.af_tower_update_device.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_int64), C.c_int32]
         L.af_tower_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
         L.af_tower_debug_weights.restype = C.c_int64
+        # the int8 residual blocks (csrc/af_tower_i8.hip)
+        L.af_tower_i8_enable.argtypes = [vp, fp, C.c_int32]
+        L.af_tower_i8_plane_bytes.argtypes = [vp]
+        L.af_tower_i8_plane_bytes.restype = C.c_int64
+        L.af_tower_forward_i8.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
+        L.af_tower_conv_i8.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32]
+        L.af_tower_quantize_i8.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.af_tower_i8_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
+        L.af_tower_i8_debug_weights.restype = C.c_int64
         L.af_tower_strerror.argtypes = [C.c_int]
         L.af_tower_strerror.restype = C.c_char_p
         _lib = L
@@ -72,19 +81,48 @@ def update_names(blocks):
     return names
 
 
+PRECISIONS = ("bf16", "int8")
+
+
+def check_precision(precision, board_size, act_scales):
+    """What a tower can be built with, checked before anything touches the GPU: ValueError for an unknown precision, for int8 on
+    a board other than 11x11 (the int8 kernels exist for that size only) and for int8 without activation scales."""
+    if precision not in PRECISIONS:
+        raise ValueError("unknown precision %r: expected one of %s" % (precision, ", ".join(PRECISIONS)))
+    if precision == "int8":
+        if board_size != 11:
+            raise ValueError("precision='int8' is built for 11x11 boards only, not %dx%d" % (board_size, board_size))
+        if act_scales is None:
+            raise ValueError("precision='int8' needs act_scales (DeepResNet.calibrate_int8)")
+    elif act_scales is not None:
+        raise ValueError("act_scales given with precision=%r" % (precision,))
+
+
 def tune(key, value):
     _check(lib().af_tower_tune(key, value), "af_tower_tune")
 
 
 class HipTower(object):
-    """blocks = list of dicts with torch tensors res/c1/c2 = (weight OIHW, bias), as DeepResNet.tower holds them."""
+    """blocks = list of dicts with torch tensors res/c1/c2 = (weight OIHW, bias), as DeepResNet.tower holds them.
+    precision="int8" (11x11 only) with act_scales = the 2 * blocks activation scales of alphafive_amd/tower_i8.py: the handle is
+    enabled for int8 BEFORE the weights are set, so every pack path — the setters here, load_device — also packs the int8
+    weights from the same fp32 sources, and the tower owns the two int8 activation buffers forward_i8 runs through."""
 
-    def __init__(self, blocks, board_size, width, max_batch, device, stem=None, vconv=None, pconv=None, dense=None):
+    def __init__(self, blocks, board_size, width, max_batch, device, stem=None, vconv=None, pconv=None, dense=None,
+                 precision="bf16", act_scales=None):
+        check_precision(precision, board_size, act_scales)
         self.S, self.width, self.max_batch, self.device = board_size, width, max_batch, torch.device(device)
         self._h = C.c_void_p()
         self.blocks = len(blocks)
+        self.precision = precision
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _check(lib().af_tower_create(board_size, width, len(blocks), idx, C.byref(self._h)), "af_tower_create")
+        if precision == "int8":
+            self.enable_i8(act_scales)
+            plane = int(lib().af_tower_i8_plane_bytes(self._h))
+            # C16 activations [B][width/16][PIX][16]; zero borders are never written by the kernels
+            self.xq = torch.zeros((max_batch, width // 16, plane // (width // 16) // 16, 16), dtype=torch.int8, device=self.device)
+            self.gq = torch.zeros_like(self.xq)
         for b, blk in enumerate(blocks):
             self.set_block(b, blk)
         if stem is not None:
@@ -177,6 +215,45 @@ class HipTower(object):
     def forward(self, B):
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().af_tower_forward(self._h, stream, self.x.data_ptr(), self.g.data_ptr(), B), "af_tower_forward")
+
+    # ---- int8 residual blocks ----
+    def enable_i8(self, act_scales):
+        """af_tower_i8_enable: stores the activation scales; called again with new ones it re-packs the int8 weights in place
+        (synchronises the device)."""
+        a = np.ascontiguousarray(np.asarray(act_scales, np.float32).reshape(-1))
+        _check(lib().af_tower_i8_enable(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0]), "af_tower_i8_enable")
+        self.act_scales = a.copy()
+
+    def forward_i8(self, B):
+        """The blocks in int8: quantises the stem's output in self.x, runs every block through xq / gq and leaves the last block's
+        bf16 output in self.x, where heads() reads it.  The persistent kernels at every batch."""
+        if self.precision != "int8":
+            raise TowerError("forward_i8: this tower was built with precision=%r" % (self.precision,), -3)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_forward_i8(self._h, stream, self.x.data_ptr(), self.xq.data_ptr(), self.gq.data_ptr(), B),
+               "af_tower_forward_i8")
+
+    def quantize_i8(self, x, xq, B):
+        """Tests: the entry quantiser alone, bf16 C8 tensor x -> int8 C16 tensor xq."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_quantize_i8(self._h, stream, x.data_ptr(), xq.data_ptr(), B), "af_tower_quantize_i8")
+
+    def conv_i8(self, block, second, inp, inp2, out, B):
+        """Tests: one int8 layer (af_tower_conv_i8); out int8 C16 or bf16 C8, by its dtype."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_conv_i8(self._h, stream, block, int(second), inp.data_ptr(), inp2.data_ptr() if inp2 is not None else None,
+                                      out.data_ptr(), int(out.dtype == torch.bfloat16), B), "af_tower_conv_i8")
+
+    def debug_weights_i8(self):
+        """Tests: the int8 weight-derived buffers as bytes, in af_tower_i8_debug_weights' order (4 per block, then the scales)."""
+        out = []
+        for i in range(4 * self.blocks + 1):
+            size = lib().af_tower_i8_debug_weights(self._h, i, None, 0)
+            _check(size, "af_tower_i8_debug_weights")
+            buf = np.empty(size, np.uint8)
+            _check(lib().af_tower_i8_debug_weights(self._h, i, buf.ctypes.data_as(C.c_void_p), size), "af_tower_i8_debug_weights")
+            out.append(buf)
+        return out
 
     def forward_small(self, B):
         """forward() on the tile-parallel kernel (af_tower_forward_small): the same bits at any batch, faster up to small_batch."""

@@ -137,6 +137,46 @@ int64_t af_tower_debug_weights(af_tower* t, int32_t index, void* host_out, int64
  * setting as it was. */
 int af_tower_tune(int32_t key, int32_t value);
 
+/* ---- int8 (W8A8) residual blocks, opt-in, S = 11 only ----
+ * The residual blocks with int8 weights and int8 stored activations on v_mfma_i32_32x32x32_i8 (csrc/af_tower_i8.hip); stem, heads
+ * and dense layers stay on the bf16 kernels above, and nothing above changes its bits on a handle that enables this.  The
+ * arithmetic — activation scales, weight quantisation per cout, the projection folded into the second convolution's accumulator,
+ * the epilogue's order — and the byte layouts are specified once, in numpy, by alphafive_amd/tower_i8.py; kernels and packers are
+ * held to it bit for bit.  Every call below returns AF_TOWER_ERR_ARG on an S = 15 handle.
+ *
+ * Activation layout "C16": int8 [batch][8][PIX = 144][16], pixel (y, x) at unit 11*(y+1) + x — C8 with 16 one-byte channels per
+ * 16-byte unit; the zero rows above and below the board are never written.  The caller owns the two int8 buffers.
+ *
+ * af_tower_i8_enable: act_scales_host holds n = 2 * blocks fp32 scales in the order h_0, g_0, h_1, g_1, ... (h_b: input of block b,
+ * g_b: output of its first convolution; the last block's output stays bf16).  A wrong n or a scale that is not finite and
+ * positive is AF_TOWER_ERR_ARG.  The call waits for the device, stores the scales and their reciprocals in device memory and marks
+ * the handle: from then on every pack path — the host setters and af_tower_update_device — also runs the int8 packers over the
+ * blocks, device kernels that read the same fp32 sources, reduce the per-cout absmax on the device and write the int8 fragment
+ * streams, the multipliers m[c] and the biases (launches only, nothing read back, so af_tower_update_device stays legal under
+ * capture and a captured int8 forward replays with the new weights: scales and multipliers are read from device memory, never
+ * passed by value).  They also keep the blocks' fp32 tensors as packed (1.25 MB per block, inside the one allocation of
+ * af_tower_create), because new scales change the folded projection: calling af_tower_i8_enable again re-packs, in place, every
+ * block packed since the first call, and waits.  A block whose weights were set BEFORE the first enable has no int8 weights until
+ * its setter (or a device update) runs again — enable first, then set the weights, as alphafive_amd/tower_hip.py does. */
+int af_tower_i8_enable(af_tower* t, const float* act_scales_host, int32_t n);
+int64_t af_tower_i8_plane_bytes(const af_tower* t);   /* bytes per position of a C16 buffer: 18,432 (0 at S = 15) */
+/* x_dev: the stem's bf16 C8 output.  Quantises it into xq_dev, runs every block through xq_dev / gq_dev (C16, zero borders) and
+ * writes the last block's output, bf16 C8, back into x_dev, so that af_tower_heads follows unchanged.  Asynchronous on `stream`,
+ * launches only, any batch >= 1, always the persistent kernels.  AF_TOWER_ERR_STATE before af_tower_i8_enable or while a block
+ * has no int8 weights. */
+int af_tower_forward_i8(af_tower* t, void* stream, void* x_dev, void* xq_dev, void* gq_dev, int32_t batch);
+/* Tests: one layer.  second = 0: the first convolution of `block` over in_dev (in2_dev unused); second = 1: the second convolution
+ * over in_dev plus the projection of in2_dev (the block input).  out_dev is C16 int8, or bf16 C8 if out_is_bf16; an int8 output of
+ * the last block's second convolution, which has no scale, is AF_TOWER_ERR_ARG.  Honours tune key 1. */
+int af_tower_conv_i8(af_tower* t, void* stream, int32_t block, int32_t second, const void* in_dev, const void* in2_dev, void* out_dev,
+                     int32_t out_is_bf16, int32_t batch);
+/* Tests: the entry quantiser alone, bf16 C8 -> int8 C16 at the scale of h_0. */
+int af_tower_quantize_i8(af_tower* t, void* stream, const void* x_dev, void* xq_dev, int32_t batch);
+/* Tests: af_tower_debug_weights for the int8 buffers, 4 * blocks + 1 of them: 4b + 0..3 = w1q, w2q (fragment streams, uint8
+ * [2][72 | 80][64][16]), mb1, mb2 (fp32 m[128] then b[128]) of block b; the last is fp32 [2][2 * blocks], the scales and their
+ * reciprocals.  AF_TOWER_ERR_STATE before enable or for a block without int8 weights. */
+int64_t af_tower_i8_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes);
+
 int64_t af_tower_flops_per_position(const af_tower* t);   /* 2*MAC of the tower, direct convolution */
 const char* af_tower_strerror(int code);
 
