@@ -242,7 +242,8 @@ int af_train_adam(void* stream, int32_t nvars, const af_train_var* vars, float l
     int64_t total = 0;
     for (int k = 0; k < nvars; ++k) {
         const af_train_var& a = vars[k];
-        if (a.n < 0 || !a.p || !a.g || !a.m || !a.v) return AF_TRAIN_ERR_ARG;
+        // an empty variable owns no chunk, so no workgroup ever reads its pointers: a zero-size buffer's may be null
+        if (a.n < 0 || (a.n > 0 && (!a.p || !a.g || !a.m || !a.v))) return AF_TRAIN_ERR_ARG;
         if (a.n > INT32_MAX) return AF_TRAIN_ERR_RANGE;
         T.p[k] = a.p; T.g[k] = a.g; T.m[k] = a.m; T.v[k] = a.v;
         T.n[k] = (int32_t)a.n;

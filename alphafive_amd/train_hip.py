@@ -4,10 +4,14 @@
     adam        every variable's (p, g, m, v) updated in place + the L2 partial sums  one launch per 64 variables
     finalize    row_terms + L2 partials -> (total, cross_entropy, value_loss, entropy) on the device
 
-All three run on torch's current stream and never wait for the device.  adam_reference() states the Adam element in numpy
-float32, one operation per line: the kernel equals it bit for bit (tests/test_gpu_train_fused.py), the role
-replay.draw_reference has for the draw kernel.  loss_head_reference() / terms_reference() state the loss head in float64.
-train.Trainer(fused=True) is the caller.
+All three run on torch's current stream and never wait for the device.  The specifications, in numpy:
+    adam_reference          the Adam element in float32, one operation per line                        the kernel: bit for bit
+    l2_partials_reference   a chunk's sum of p * p in the header's order (strided, butterfly, waves)   the kernel: bit for bit
+    finalize_reference      the six fp64 sums in that order and the header's four expressions          the kernel: bit for bit
+    loss_head_reference     the loss head in float64 (loss_head_parts: with logsm and sum(pi)); dvalue, vsq and w * vsq bit for
+                            bit, dlogits inside the fp32 interval around ref +- 2^-40 * (w / B) * (|pi| + s * sum(pi))
+terms_reference() is finalize in float64 without an order.  tests/train_cases.py holds the cases and the comparison rules,
+tests/test_gpu_train_fused.py runs the kernels on them.  train.Trainer(fused=True) is the caller.
 """
 import ctypes as C
 import os
@@ -97,7 +101,8 @@ def adam_partials(sizes):
 
 class VarTable(object):
     """The (p, m, v, decay) side of adam()'s table, built once: ctypes arrays of at most MAX_VARS entries each, one launch per
-    array.  set_grads() fills in the side that changes every step (autograd hands out fresh gradient tensors)."""
+    array.  set_grads() fills in the side that changes every step (autograd hands out fresh gradient tensors).  An empty
+    variable is allowed: torch gives it a null pointer, which the library accepts for n = 0 and never reads."""
 
     def __init__(self, ps, ms, vs, decay):
         self.device = ps[0].device
@@ -184,8 +189,66 @@ def adam_reference(p, g, m, v, decay, lr_t, beta1, beta2, eps, l2_coef):
     return p, m, v
 
 
-def loss_head_reference(logits, value, pi, winner, weight):
-    """af_train_loss_head in float64 -> (dlogits[B][C], dvalue[B], row_terms[B][ROW_TERMS])."""
+def _tree_sum(acc):
+    """The fixed tree every block reduction of af_train.hip ends with (block_sum): acc[..., 256] holds the 256 threads' own
+    sums; a butterfly over the 64 lanes of each wave (x = x + x[lane ^ o], o = 32 .. 1: every lane ends with the same bits),
+    then the four waves as ((w0 + w1) + w2) + w3.  In acc's dtype, one IEEE add per step."""
+    x = acc.reshape(acc.shape[:-1] + (4, 64))
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        x = x + x[..., lane ^ o]
+    w = x[..., 0]
+    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+
+
+def _strided_sum(x, dtype):
+    """Thread t of 256 adds entries t, t + 256, ... of x (one dimension) in index order, from 0; then _tree_sum.  A thread's
+    sum never is -0 (it starts at +0), so padding the tail with +0 adds nothing."""
+    x = np.asarray(x, dtype).reshape(-1)
+    pad = np.zeros(-(-max(x.size, 1) // 256) * 256, dtype)
+    pad[:x.size] = x
+    acc = np.zeros(256, dtype)
+    for row in pad.reshape(-1, 256):
+        acc = acc + row
+    return _tree_sum(acc)
+
+
+def l2_partials_reference(p, decay):
+    """af_train_adam's l2_partials of one variable (p BEFORE the update) -> float32[ceil(n / ADAM_CHUNK)], in the order
+    include/af_train.h states: per chunk, thread t of 256 adds p * p of elements t, t + 256, ... in fp32, then the butterfly
+    over the 64 lanes, then the four waves in order.  0 per chunk for a variable without decay; empty for n = 0.
+    The kernel equals it bit for bit."""
+    p = np.asarray(p, np.float32).reshape(-1)
+    chunks = -(-p.size // ADAM_CHUNK)
+    if not decay or chunks == 0:
+        return np.zeros(chunks, np.float32)
+    pad = np.zeros(chunks * ADAM_CHUNK, np.float32)
+    pad[:p.size] = p
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        sq = (pad * pad).reshape(chunks, ADAM_CHUNK // 256, 256)
+        acc = np.zeros((chunks, 256), np.float32)
+        for j in range(sq.shape[1]):
+            acc = acc + sq[:, j, :]
+        out = _tree_sum(acc)
+    assert out.dtype == np.float32
+    return out
+
+
+def finalize_reference(row_terms, l2_partials, l2_coef):
+    """af_train_finalize -> float32[4] (total, cross_entropy, value_loss, entropy), bit for bit: the five column sums S_j of
+    row_terms float64[B][ROW_TERMS] and L, the sum of the fp32 partials converted to fp64, each in the strided, butterfly and
+    four-wave order of include/af_train.h in fp64; then the header's four expressions as written, each rounded to fp32 once."""
+    rows = np.asarray(row_terms, np.float64).reshape(-1, ROW_TERMS)
+    dB = np.float64(rows.shape[0])
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = [_strided_sum(rows[:, j], np.float64) for j in range(ROW_TERMS)]
+        L = _strided_sum(np.asarray(l2_partials, np.float32).astype(np.float64), np.float64)
+        total = (-(s[0] / dB) + np.float64(2.0) * (s[1] / dB)) + np.float64(np.float32(l2_coef)) * (L / np.float64(2.0))
+        return np.array([total, -(s[2] / dB), s[3] / dB, s[4] / dB], np.float64).astype(np.float32)
+
+
+def loss_head_parts(logits, value, pi, winner, weight):
+    """The float64 statement of af_train_loss_head with its intermediates -> dict(dlogits, dvalue, rows, logsm, psum)."""
     z, v, pi, zv, w = (np.asarray(a, np.float64) for a in (logits, value, pi, winner, weight))
     B = z.shape[0]
     z = z - z.max(axis=1, keepdims=True)
@@ -194,9 +257,16 @@ def loss_head_reference(logits, value, pi, winner, weight):
     vsq = (v - zv) ** 2
     ent = -(np.exp(logsm) * logsm).sum(axis=1)
     rows = np.stack([w * xent, w * vsq, xent, vsq, ent], axis=1)
-    dlogits = -(w / B)[:, None] * (pi - np.exp(logsm) * pi.sum(axis=1, keepdims=True))
+    psum = pi.sum(axis=1, keepdims=True)
+    dlogits = -(w / B)[:, None] * (pi - np.exp(logsm) * psum)
     dvalue = (4 * w / B) * (v - zv)
-    return dlogits, dvalue, rows
+    return dict(dlogits=dlogits, dvalue=dvalue, rows=rows, logsm=logsm, psum=psum[:, 0])
+
+
+def loss_head_reference(logits, value, pi, winner, weight):
+    """af_train_loss_head in float64 -> (dlogits[B][C], dvalue[B], row_terms[B][ROW_TERMS])."""
+    r = loss_head_parts(logits, value, pi, winner, weight)
+    return r["dlogits"], r["dvalue"], r["rows"]
 
 
 def terms_reference(row_terms, l2_sum, l2_coef=L2_COEF):

@@ -50,7 +50,8 @@ int af_train_loss_head(void* stream, int32_t B, int32_t C, const float* logits, 
                        const float* winner, const float* weight, float* dlogits, float* dvalue, double* row_terms);
 
 /* One variable of af_train_adam: n elements at p (parameter), g (gradient of the data terms), m, v (Adam's slots); decay != 0:
- * the variable is under the L2 penalty.  n = 0 is allowed (nothing happens to it). */
+ * the variable is under the L2 penalty.  n = 0 is allowed: nothing happens to it, it has no chunk and no partial, and its
+ * pointers are never read (they may be null, as a zero-size buffer's usually are). */
 typedef struct af_train_var {
     float* p;
     const float* g;

@@ -1,12 +1,16 @@
 """Trainer(fused=True) on the device: the three kernels of libaf_train.so (include/af_train.h) against their specifications
 (train_hip.loss_head_reference in fp64, train_hip.adam_reference bit for bit), and the Trainer built on them against the fp64
-restatement of the loss, the eager Trainer, its own checkpoints and the evaluator's weight hand-over."""
+restatement of the loss, the eager Trainer, its own checkpoints and the evaluator's weight hand-over.
+The last section holds every kernel to its specification element by element on the cases of tests/train_cases.py (the rules
+are stated there): the loss head inside 2^-40 intervals around fp64 on all five kernels, Adam, its L2 partials and finalize
+bit for bit, and four Trainer steps on three nets bit for bit from what the step really fed its kernels."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import train_cases as tc
 from conftest import GOLDEN
 from test_train_cpu import _batch
 
@@ -360,3 +364,223 @@ def test_one_fused_step_of_the_deep_net_logs_what_the_eager_one_logs():
         assert abs(mf[k] - me[k]) < 2e-5 * max(1.0, abs(me[k])), k
     m2 = fused.step(boards, weights, winner, pol, lr=1e-3)
     assert np.isfinite(list(m2.values())).all() and m2["total"] != mf["total"]
+
+
+# ---------------------------------------------------------------- element by element, on the cases of tests/train_cases.py
+SENTINEL = -777.25
+
+
+def _dev(a, pad=0):
+    """A device copy of a host array, `pad` sentinel elements (rows) longer."""
+    import torch
+    t = torch.tensor(np.asarray(a))
+    if pad:
+        t = torch.cat([t, torch.full((pad,) + tuple(t.shape[1:]), SENTINEL, dtype=t.dtype)])
+    return t.cuda()
+
+
+def _loss_head_abi(inputs):
+    """af_train_loss_head through the C ABI, outputs two rows longer than B and pre-filled -> host (dlogits, dvalue, rows), B + 2 rows."""
+    import torch
+    from alphafive_amd import train_hip
+    B, Cn = inputs[0].shape
+    dev = [_dev(a) for a in inputs]
+    dl = torch.full((B + 2, Cn), SENTINEL, dtype=torch.float32, device="cuda")
+    dv = torch.full((B + 2,), SENTINEL, dtype=torch.float32, device="cuda")
+    rows = torch.full((B + 2, train_hip.ROW_TERMS), SENTINEL, dtype=torch.float64, device="cuda")
+    rc = train_hip.lib().af_train_loss_head(torch.cuda.current_stream().cuda_stream, B, Cn, *(t.data_ptr() for t in dev),
+                                            dl.data_ptr(), dv.data_ptr(), rows.data_ptr())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return dl.cpu().numpy(), dv.cpu().numpy(), rows.cpu().numpy()
+
+
+@pytest.mark.parametrize("K", [1, 2, 4, 8, 16])
+def test_loss_head_kernel_meets_the_interval_rule_on_every_case(K):
+    """af_train_loss_head_kernel<K> on every case of tc.HEAD_CASES it runs: tc.check_loss_head (dlogits inside its 2^-40
+    interval around fp64, dvalue / vsq / w * vsq bit for bit, the three sums inside their bounds), nothing written at or
+    past row B, the same bits on a rerun.  Measured on an MI355X: profiles/train_fused.md."""
+    cases = [(B, Cn) for B, Cn in tc.HEAD_CASES if tc.per_lane(Cn) == K]
+    assert cases
+    total = dict(n=0, near=0, flips=0)
+    worst = worst_rows = relative_only = 0.0
+    for B, Cn in cases:
+        inputs = tc.head_case(B, Cn)
+        dl, dv, rows = _loss_head_abi(inputs)
+        for name, a in (("dlogits", dl), ("dvalue", dv), ("row_terms", rows)):
+            assert (a[B:] == SENTINEL).all(), "(%d, %d): %s written at or past row B" % (B, Cn, name)
+        r = tc.check_loss_head(inputs, dl[:B], dv[:B], rows[:B], what="kernel<%d> (%d, %d)" % (K, B, Cn), parts=tc.head_reference(B, Cn))
+        print("kernel<%d> (%d, %d): worst |got - ref| / e %.3g, worst row-term ratio %.3g, %d of %d near, %d of them not float32(ref)"
+              % (K, B, Cn, r["worst"], r["worst_rows"], r["near"], r["n"], r["flips"]))
+        worst, worst_rows, relative_only = max(worst, r["worst"]), max(worst_rows, r["worst_rows"]), max(relative_only, r["relative_only"])
+        for k in total:
+            total[k] += r[k]
+        again = _loss_head_abi(inputs)
+        assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip((dl, dv, rows), again)), (B, Cn)
+    print("af_train_loss_head_kernel<%d>: %d cases, %d elements, worst |got - ref| / e %.3g, worst row-term ratio %.3g, near share %.4f %% "
+          "(%d elements, %d not float32(ref)); xent / ent against 2^-40 * sum |term| alone: %.3g"
+          % (K, len(cases), total["n"], worst, worst_rows, 100.0 * total["near"] / max(1, total["n"]), total["near"], total["flips"], relative_only))
+    assert worst <= 1 and worst_rows <= 1
+
+
+def _adam_on_device(p, g, m, v, decay, lr_t, n_partials):
+    """One train_hip.adam over host arrays -> (p, m, v, partials) as the device left them; the partials buffer is two longer
+    than needed and must keep its sentinel there."""
+    import torch
+    from alphafive_amd import train_hip
+    dp, dg, dm, dv = ([_dev(a) for a in arrs] for arrs in (p, g, m, v))
+    partials = torch.full((n_partials + 2,), SENTINEL, device="cuda")
+    assert train_hip.adam(list(zip(dp, dg, dm, dv, decay)), lr_t, BETA1, BETA2, EPS, L2, partials) == n_partials
+    host = lambda ts: [t.cpu().numpy() for t in ts]  # noqa: E731
+    out = partials.cpu().numpy()
+    assert (out[n_partials:] == SENTINEL).all()
+    return host(dp), host(dm), host(dv), out[:n_partials]
+
+
+def test_adam_and_its_partials_on_planted_values_bit_for_bit():
+    """tc.adam_case(): four steps over every size around the wave, the workgroup and the chunk, one variable carrying subnormal
+    g * g, v, m and l2_coef * p, overflow to inf, +-inf and NaN gradients, signed zeros and p = 3e38: p, m, v and every L2
+    partial are the references' bits (NaN where the reference is NaN)."""
+    import torch
+    from alphafive_amd import train_hip
+    c = tc.adam_case()
+    dp, dm, dv = ([_dev(a) for a in c[k]] for k in "pmv")
+    table = train_hip.VarTable(dp, dm, dv, c["decay"])
+    partials = torch.full((table.n_partials + 2,), SENTINEL, device="cuda")
+    p, m, v = c["p"], c["m"], c["v"]
+    n = 0
+    for t in range(tc.ADAM_STEPS):
+        table.set_grads([_dev(a) for a in c["g"][t]])
+        assert train_hip.adam(table, c["lr_t"][t], BETA1, BETA2, EPS, L2, partials) == table.n_partials
+        ref = tc.adam_step_reference(p, c["g"][t], m, v, c["decay"], c["lr_t"][t])
+        got = tuple([x.cpu().numpy() for x in ts] for ts in (dp, dm, dv)) + (partials.cpu().numpy()[:table.n_partials],)
+        n += tc.check_adam(got, ref, "step %d" % (t + 1))
+        assert (partials.cpu().numpy()[table.n_partials:] == SENTINEL).all()
+        p, m, v = ref[:3]
+    print("Adam on planted values: %d elements over %d steps bit for bit" % (n, tc.ADAM_STEPS))
+
+
+@pytest.mark.parametrize("nvars", [64, 65, 129])
+def test_adam_tables_exactly_full_one_over_and_three_launches(nvars):
+    p, g, m, v, decay = tc.table_case(nvars)
+    got = _adam_on_device(p, g, m, v, decay, tc.lr_t(3), nvars)
+    tc.check_adam(got, tc.adam_step_reference(p, g, m, v, decay, tc.lr_t(3)), "%d variables" % nvars)
+
+
+def test_adam_skips_empty_variables_first_in_the_middle_and_last():
+    """n = 0 entries with valid pointers (the C ABI) and with the null pointers of empty tensors (VarTable): their buffers keep
+    their sentinel, they own no partial, and their neighbours' chunks are right."""
+    import torch
+    from alphafive_amd import train_hip
+    rng = np.random.RandomState(21)
+    sizes = [0, 5, 2049, 0, 0, 64, 0]
+    decay = [True, True, True, False, True, False, True]
+    p = [(rng.randn(n) * 0.1).astype(np.float32) for n in sizes]
+    g, m = ([(rng.randn(n) * 1e-2).astype(np.float32) for n in sizes] for _ in range(2))
+    v = [(rng.rand(n) * 1e-4).astype(np.float32) for n in sizes]
+    ref = tc.adam_step_reference(p, g, m, v, decay, tc.lr_t(2))
+    assert ref[3].size == 1 + 2 + 1
+    # the null pointers of empty tensors, through VarTable
+    assert torch.empty(0, device="cuda").data_ptr() == 0
+    tc.check_adam(_adam_on_device(p, g, m, v, decay, tc.lr_t(2), 4), ref, "empty tensors")
+    # valid pointers: every empty entry points at four sentinel elements of its own
+    bufs = [[_dev(a, pad=4 if a.size == 0 else 0) for a in arrs] for arrs in (p, g, m, v)]
+    arr = (train_hip.Var * len(sizes))()
+    for k, e in enumerate(arr):
+        e.p, e.g, e.m, e.v = (bufs[j][k].data_ptr() for j in range(4))
+        e.n, e.decay = sizes[k], int(decay[k])
+    partials = torch.full((6,), SENTINEL, device="cuda")
+    rc = train_hip.lib().af_train_adam(torch.cuda.current_stream().cuda_stream, len(sizes), arr, tc.lr_t(2), BETA1, BETA2, EPS, L2,
+                                       partials.data_ptr())
+    assert rc == 4
+    torch.cuda.synchronize()
+    host = [[t.cpu().numpy() for t in ts] for ts in bufs]
+    for k, n in enumerate(sizes):
+        if n == 0:
+            assert all((host[j][k] == SENTINEL).all() and host[j][k].size == 4 for j in range(4)), k
+    cut = lambda ts: [a[:n] for a, n in zip(ts, sizes)]  # noqa: E731
+    out = partials.cpu().numpy()
+    tc.check_adam((cut(host[0]), cut(host[2]), cut(host[3]), out[:4]), ref, "valid pointers")
+    assert (out[4:] == SENTINEL).all()
+    # a table of empty variables only launches nothing
+    assert train_hip.lib().af_train_adam(None, 1, arr, tc.lr_t(2), BETA1, BETA2, EPS, L2, partials.data_ptr()) == 0
+
+
+def test_finalize_equals_its_reference_bit_for_bit_on_every_case():
+    """B in {1, 255, 256, 257, 1000} x n_partials in {0, 1, 255, 256, 257, 1500}: the strided loop over more than 256 entries on
+    both inputs, cancelling row terms so that the order of the fp64 adds shows in the fp32 results."""
+    from alphafive_amd import train_hip
+    for B, P in tc.FIN_CASES:
+        rows, partials = tc.finalize_case(B, P)
+        got = train_hip.finalize(_dev(rows), _dev(partials, pad=2) if P else None, P, L2).cpu().numpy()
+        tc.check_finalize(got, rows, partials, L2, "finalize B = %d, %d partials" % (B, P))
+
+
+def _decay_by_name(name):
+    return "bias" not in name and "bn" not in name                     # train.Trainer._init_fused
+
+
+@pytest.mark.parametrize("kind,nvars,launches", [("net42", 42, 1), ("deep2", 24, 1), ("deep9", 66, 2)])
+def test_four_fused_steps_are_the_specifications_bit_for_bit(kind, nvars, launches, monkeypatch):
+    """Four steps, a different batch each, with what the step feeds its kernels recorded (the gradients VarTable.set_grads
+    receives, the loss head's inputs and outputs): params, m and v of every variable after each step are adam_reference of the
+    state before it with the recorded gradient in the variable's logical layout, the name rule for decay and float32(lr_t) of
+    that t; the recorded dlogits / dvalue / row terms meet tc.check_loss_head on the recorded logits; the four logged scalars
+    are finalize_reference of the recorded rows and l2_partials_reference of the parameters before the step.  Recording the
+    gradients makes this independent of autograd's reproducibility."""
+    import torch
+    from alphafive_amd import network_deep, train, train_hip
+    if kind == "net42":
+        from alphafive_amd.network import ResNet
+        Sx, nb, kw = 6, 33, {}
+        net = ResNet(Sx, device="cpu", seed=4)
+    else:
+        Sx, nb = 7, 9
+        net = network_deep.DeepResNet(Sx, blocks=2 if kind == "deep2" else 9, width=32, device="cpu", dtype=torch.float32, seed=4)
+        kw = dict(forward=train.forward_train_deep, shapes=net.variable_shapes())
+    tr = _trainer(net.variables, S=Sx, fused=True, **kw)
+    names = list(tr.params)
+    assert len(names) == nvars and len(tr._table.groups) == launches
+    rec = {}
+    set_grads, loss_head = tr._table.set_grads, train_hip.loss_head
+
+    def record_grads(grads):
+        grads = list(grads)
+        rec["g"] = [g.detach().clone() for g in grads]
+        return set_grads(grads)
+
+    def record_head(*inputs):
+        out = loss_head(*inputs)
+        rec["head"] = [t.detach().clone() for t in inputs + tuple(out)]
+        return out
+
+    monkeypatch.setattr(tr._table, "set_grads", record_grads)
+    monkeypatch.setattr(train_hip, "loss_head", record_head)
+    compared = 0
+    for t in range(1, 5):
+        boards, weights, winner, pol = _batch(Sx, nb, seed=40 + t)
+        before = tr.state_dict()
+        rec.clear()
+        metrics = tr.step(boards, weights, winner, pol, lr=1e-3)
+        after = tr.state_dict()
+        assert after["t"] == t and len(rec["g"]) == nvars
+        lr_t = np.float32(_lr_t(t))
+        partials = []
+        for k, g in zip(names, rec["g"]):
+            p0 = before["params"][k]
+            assert tuple(g.shape) == p0.shape, k
+            ref = train_hip.adam_reference(p0, g.cpu().numpy(), before["m"][k], before["v"][k], _decay_by_name(k), lr_t,
+                                           BETA1, BETA2, EPS, train_hip.L2_COEF)
+            for key, r in zip(("params", "m", "v"), ref):
+                compared += tc.check_bits(after[key][k], r, "%s step %d %s %s" % (kind, t, key, k))
+            partials.append(train_hip.l2_partials_reference(p0, _decay_by_name(k)))
+        head = [x.cpu().numpy() for x in rec["head"]]
+        assert np.array_equal(head[2], pol) and np.array_equal(head[3], winner) and np.array_equal(head[4], weights)
+        r = tc.check_loss_head(tuple(head[:5]), *head[5:], what="%s step %d" % (kind, t))
+        terms = train_hip.finalize_reference(head[7], np.concatenate(partials), train_hip.L2_COEF)
+        got = np.array([metrics[k] for k in ("total", "cross_entropy", "value_loss", "entropy")], np.float32)
+        assert [float(x) for x in got] == [metrics[k] for k in ("total", "cross_entropy", "value_loss", "entropy")]
+        tc.check_bits(got, terms, "%s step %d logged scalars" % (kind, t))
+        compared += r["n"] + 4
+    print("%s: %d elements compared over four steps (%d variables, %d partials, %d Adam launches per step)"
+          % (kind, compared, nvars, tr._table.n_partials, launches))
