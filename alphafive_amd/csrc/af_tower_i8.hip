@@ -27,6 +27,9 @@
 // in LDS (1 KB, read once per position and accumulator set); r_out is read from device memory at the top.  Scales and multipliers
 // never travel by value, so a captured launch follows a re-pack.
 //
+// af_tower_conv_i8_small<PROJ, OBF> is the same layer for a handful of positions, one workgroup per pixel tile with the weights
+// streamed (af_tower_forward_i8_small; its own comment, behind the kernel above; the same bits).
+//
 // The packers (af_tower_pack_i8_kernel) and the entry quantiser (af_tower_quantize_i8_kernel) are at the end, with the host part.
 #include <hip/hip_runtime.h>
 
@@ -228,6 +231,131 @@ __global__ __launch_bounds__(256, 1) void af_tower_conv_i8_kernel(I8Args A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// af_tower_conv_i8_small<PROJ, OBF>: the same layer for a handful of positions (af_tower_forward_i8_small), after
+// af_tower_bf16.hip's af_tower_conv_small.  The kernel above is weight-stationary: a workgroup loads its 147 / 164 KB of A
+// fragments before its first MFMA and then walks positions, which at batch 1 is one workgroup on one CU.  Here the work is split
+// the other way:
+//   - one workgroup per (position, pixel tile): grid = batch * 4, workgroup b = tile b & 3 of position b >> 2; its 4 waves are
+//     the 4 cout tiles of 32: wave w = cout tile w & 1 of cout half w >> 1, i.e. fragments f = 2 * k-step + (w & 1) of half
+//     w >> 1 of the stream [2][NS][64][16] the kernel above keeps resident — no other packer, no other buffer;
+//   - the workgroup stages the position's plane (PROJ: and the block-input plane) once, single-buffered, with stage_round16 into
+//     the LDS layout above (the second slot stays unused), so the zero region, the edge bases and the tap offsets are the same;
+//   - a wave runs its tile's 36 / 40 MFMAs into ONE accumulator — a single chain of v_mfma_i32_32x32x32_i8, in the order above
+//     (PROJ: the four projection steps first, then tap major, cin step minor);
+//   - the A fragments are not resident: fragment i of that order streams through a ring of kSmallA8 register sets, its load
+//     issued kSmallA8 MFMAs before its use, so the first MFMA waits for the planes and ONE fragment, not for all of them.  The
+//     prefill is issued behind the staging loads and in front of the wait that counts them out: loads return in order, so
+//     vmcnt(kSmallA8) means every LDS-DMA piece has landed;
+//   - the epilogue is the one above for the lane's 16 couts: fmaf(float(acc), m, b), elu1, then multiply by r_out, rint, clamp
+//     and one 16-byte C16 store, or (OBF) the bf16 rounding and the two C8 stores.  m, b and r_out are read from device memory
+//     (a lane's 16 + 16 + 1 words, behind the barrier), never passed by value: a captured launch follows a re-pack.
+// The int32 accumulator is exact in any order and the epilogue is the same sequence on the same operands: bit-identical to
+// af_tower_conv_i8_kernel.  Workgroups are independent: no hand-over, no waiting on each other, no atomics.
+// IN PLACE.  A block's second convolution runs in place (out = in2 = xq), and the four tile workgroups of a position run
+// concurrently, so a workgroup may stage units of xq that a sibling has already overwritten.  xq is read only through the 1x1
+// projection, at the lane's OWN pixel: the centre unit of a pixel this workgroup computes, which nobody else writes and which
+// this workgroup writes after its own staging has landed (the wait and the barrier below are in front of every store).  The 3x3
+// window reads gq, which this launch does not write.  A lane whose pixel does not exist reads pixel 0's unit of another tile
+// in the projection (whatever it finds) and the zero region in the window, and never stores.  The padded fifth staging round
+// re-reads the plane's first unit into the slot's pad, which no tap reaches (the static_asserts above).
+// Ring depth by measurement (profiles/tower_int8_small.md): 8, 12 and 16 are level, 24, 32 (af_tower_conv_small's) and 36 (all of
+// them in front) each a little slower at batches 1, 8 and 64; 16 is the deepest of the level ones.
+constexpr int kSmallA8 = 16;     // A-fragment ring: 16 KB per wave in flight
+constexpr int kSmallB8 = 8;      // B-fragment ring, as af_tower_conv_small's
+template <bool PROJ, bool OBF>
+__global__ __launch_bounds__(256) void af_tower_conv_i8_small(I8Args A) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];         // [256 B][g][-]([h])[zero region][-]: the layout above
+    constexpr int NK = PROJ ? 40 : 36, NS = 2 * NK, NPK = PROJ ? 4 : 0;  // MFMAs of the chain, fragments per cout half of the stream, projection steps
+    static_assert(kSmallA8 <= 63 && kSmallA8 <= NK, "the ring's prefill is counted on vmcnt");
+    const int lane = threadIdx.x & 63, kg = lane >> 5, nn = lane & 31;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lds0 = (uint32_t)(uintptr_t)smem + kLds0;
+    const int pos = (int)(blockIdx.x >> 2), j = (int)(blockIdx.x & 3);  // position (< batch by the grid), pixel tile
+    for (uint32_t u = threadIdx.x; u < kZero16 / 16; u += 256) *reinterpret_cast<uint4*>(smem + zero_off(PROJ) + u * 16) = uint4{0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) stage_round16(lds0, wv, A.in, pos, 0u, r);
+    if (PROJ) {
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) stage_round16(lds0, wv, A.in2, pos, 2u * kSlot, r);
+    }
+    // A fragment of MFMA i: the projection's (k-steps 36..39 of the stream) first
+    const uint4* wp = A.w + ((size_t)(wv >> 1) * NS * 64 + (wv & 1u) * 64 + lane);
+    auto frag = [&](int i) -> i32x4 {
+        const uint4 v = wp[(i < NPK ? 36 + i : i - NPK) * 128];
+        i32x4 f;
+        __builtin_memcpy(&f, &v, 16);
+        return f;
+    };
+    i32x4 ra[kSmallA8];
+#pragma unroll
+    for (int i = 0; i < kSmallA8; ++i) ra[i] = frag(i);
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(kSmallA8) : "memory");   // planes landed, zero region written
+    __builtin_amdgcn_s_barrier();
+    // the lane's 16 couts 32 wv + 16 kg + r: channel group 2 wv + kg of C16
+    const uint32_t grp = 2u * wv + (uint32_t)kg;
+    float m_r[16], b_r[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { m_r[r] = A.mb[16u * grp + r]; b_r[r] = A.mb[128u + 16u * grp + r]; }
+    float rq = 0.0f;
+    if (!OBF) rq = A.r_out[0];
+    // the lane's pixel of tile j: bases as in the kernel above, for that one tile
+    const int n = 32 * j + nn;
+    const bool ok = n < G::NPIX;
+    const int nc = ok ? n : 0;
+    const int px = nc % G::S;
+    const uint32_t lb = kLds0 + (uint32_t)(kg * G::LPIX + nc + G::S - (G::S + 1)) * 16u;
+    const uint32_t ob = (uint32_t)(nc + G::S) * 16u;
+    const uint32_t zb = zero_off(PROJ) + (lb & 255u);
+    const uint32_t bC = !ok ? zb : lb, bL = px == 0 ? zb : bC, bR = px == G::S - 1 ? zb : bC;
+    auto rd = [&](int i) -> i32x4 {
+        if (i < NPK) return *reinterpret_cast<const i32x4*>(smem + 2u * kSlot + lb + (uint32_t)(2 * i * G::LPIX + G::S + 1) * 16u);
+        const int s_ = i - NPK, t = s_ >> 2, cc = s_ & 3;
+        const uint32_t base = t % 3 == 0 ? bL : (t % 3 == 2 ? bR : bC);
+        return *reinterpret_cast<const i32x4*>(smem + base + (uint32_t)(2 * cc * G::LPIX + (t / 3) * G::S + (t % 3)) * 16u);
+    };
+    i32x4 rb[kSmallB8];
+#pragma unroll
+    for (int i = 0; i < kSmallB8; ++i) rb[i] = rd(i);
+    i32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0;
+    __builtin_amdgcn_sched_barrier(0);                       // the ring's first reads stay in front: the groups below would take them one by one
+#pragma clang loop unroll(full)
+    for (int i = 0; i < NK; ++i) {
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra[i % kSmallA8], rb[i % kSmallB8], acc, 0, 0, 0);
+        if (i + kSmallB8 < NK) rb[i % kSmallB8] = rd(i + kSmallB8);
+        if (i + kSmallA8 < NK) ra[i % kSmallA8] = frag(i + kSmallA8);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+    }
+    float y[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) y[r] = elu1(__fmaf_rn((float)acc[r], m_r[r], b_r[r]));
+    if (OBF) {
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            bf16x8_t v;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (__bf16)y[8 * hf + e];
+            if (ok) *reinterpret_cast<bf16x8_t*>(A.out + (size_t)pos * kPlane8 + (uint32_t)((2 * grp + hf) * G::PIX) * 16u + ob) = v;
+        }
+    } else {
+        uint32_t d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            d[k] = 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float q = fminf(fmaxf(__builtin_rintf(__fmul_rn(y[4 * k + e], rq)), -127.0f), 127.0f);
+                d[k] |= ((uint32_t)(int)q & 255u) << (8 * e);
+            }
+        }
+        if (ok) *reinterpret_cast<uint4*>(A.out + (size_t)pos * kPlane16 + (uint32_t)(grp * G::PIX) * 16u + ob) = uint4{d[0], d[1], d[2], d[3]};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Entry quantiser: bf16 C8 -> int8 C16, q = clamp(rint(fp32(x) * r), -127, 127).  A thread owns one C16 unit of a board pixel: two
 // 16-byte loads (channel octets 2k, 2k + 1 of the pixel), one 16-byte vector store.  The zero rows are not touched.
 __global__ __launch_bounds__(256) void af_tower_quantize_i8_kernel(const char* x, char* xq, const float* r, int batch) {
@@ -365,6 +493,17 @@ constexpr I8Kernel kI8[4] = {
     {af_tower_conv_i8_kernel<true, false, kConvDepth>, true, false},   {af_tower_conv_i8_kernel<true, true, kConvDepth>, true, true},
 };
 
+// af_tower_forward_i8_small's kernels, by (PROJ, OBF) as kI8
+constexpr I8Kernel kI8Small[4] = {
+    {af_tower_conv_i8_small<false, false>, false, false}, {af_tower_conv_i8_small<false, true>, false, true},
+    {af_tower_conv_i8_small<true, false>, true, false},   {af_tower_conv_i8_small<true, true>, true, true},
+};
+// af_tower_i8_small_batch: the largest batch up to which the whole evaluation was measured faster on af_tower_forward_i8_small
+// than on af_tower_forward_i8 (profiles/tower_int8_small.md: medians apart by more than both forms' min..max spreads together;
+// measured at 1, 2, 4, ... 256: the small form wins by 62 us of 186 at 64; at 128 it is 14 us ahead, inside the spreads, and at
+// 256 it loses).
+constexpr int32_t kSmallBatchI8 = 64;
+
 size_t padded(int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); }
 int64_t act_bytes(const af_tower* t) { return (int64_t)4 * t->blocks * 4; }
 
@@ -389,6 +528,18 @@ int launch_conv(af_tower* t, hipStream_t st, int b, bool second, const void* in,
     return AF_TOWER_OK;
 }
 
+// the tile-parallel form: one workgroup per pixel tile of a position, whatever the chip and tune key 1
+void launch_conv_small(af_tower* t, hipStream_t st, int b, bool second, const void* in, const void* in2, void* out, bool obf, int batch) {
+    I8Args a;
+    a.in = static_cast<const char*>(in); a.in2 = static_cast<const char*>(in2);
+    a.w = reinterpret_cast<const uint4*>(t->qbuf[4 * b + (second ? kW2q : kW1q)]);
+    a.mb = reinterpret_cast<const float*>(t->qbuf[4 * b + (second ? kMb2 : kMb1)]);
+    a.r_out = t->act + 2 * t->blocks + (obf ? 0 : 2 * b + 1 + (second ? 1 : 0));
+    a.out = static_cast<char*>(out); a.batch = batch;
+    for (const I8Kernel& k : kI8Small)
+        if (k.proj == second && k.obf == obf) hipLaunchKernelGGL(k.fn, dim3((unsigned)batch * 4u), dim3(256), lds_bytes(second), st, a);
+}
+
 void launch_quantize(af_tower* t, hipStream_t st, const void* x, void* xq, int batch) {
     const int64_t blocks = ((int64_t)batch * 8 * G::NPIX + 255) / 256;
     hipLaunchKernelGGL(af_tower_quantize_i8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st,
@@ -408,6 +559,8 @@ int af_tower_i8_carve(af_tower* t, char* p) {
     if (t->S != 11) return AF_TOWER_OK;
     for (const I8Kernel& k : kI8)
         TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const I8Kernel& k : kI8Small)
+        TW_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(k.proj)));
     for (int b = 0; b < t->blocks; ++b)
         for (int k = 0; k < 4; ++k) { t->qbuf.push_back(p); p += padded(kQBytes[k]); }
     t->act = reinterpret_cast<float*>(p); p += padded(act_bytes(t));
@@ -495,6 +648,32 @@ int af_tower_forward_i8(af_tower* t, void* stream, void* x_dev, void* xq_dev, vo
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;
 }
+
+int af_tower_conv_i8_small(af_tower* t, void* stream, int32_t block, int32_t second, const void* in_dev, const void* in2_dev, void* out_dev,
+                           int32_t out_is_bf16, int32_t batch) {
+    if (!t || t->S != 11 || block < 0 || block >= t->blocks || !in_dev || (second && !in2_dev) || !out_dev || batch < 1) return AF_TOWER_ERR_ARG;
+    if (second && !out_is_bf16 && block == t->blocks - 1) return AF_TOWER_ERR_ARG;      // the last block's output has no int8 scale
+    if (!t->i8 || !t->qset[block]) return AF_TOWER_ERR_STATE;
+    launch_conv_small(t, static_cast<hipStream_t>(stream), block, second != 0, in_dev, in2_dev, out_dev, out_is_bf16 != 0, batch);
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
+
+int af_tower_forward_i8_small(af_tower* t, void* stream, void* x_dev, void* xq_dev, void* gq_dev, int32_t batch) {
+    if (!t || t->S != 11 || !x_dev || !xq_dev || !gq_dev || batch < 1) return AF_TOWER_ERR_ARG;
+    if (!ready(t)) return AF_TOWER_ERR_STATE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    launch_quantize(t, st, x_dev, xq_dev, batch);
+    for (int b = 0; b < t->blocks; ++b) {
+        const bool last = b == t->blocks - 1;
+        launch_conv_small(t, st, b, false, xq_dev, nullptr, gq_dev, false, batch);
+        launch_conv_small(t, st, b, true, gq_dev, xq_dev, last ? x_dev : xq_dev, last, batch);
+    }
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
+
+int32_t af_tower_i8_small_batch(const af_tower* t) { return t && t->S == 11 ? kSmallBatchI8 : 0; }
 
 int64_t af_tower_i8_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes) {
     if (!t || t->S != 11 || index < 0 || index > 4 * t->blocks) return AF_TOWER_ERR_ARG;

@@ -34,7 +34,7 @@ def variable_shapes(board_size, blocks=8, width=128):
 
 class _HipEvaluator(object):
     """planes -> (prob, value) on the hand-written kernels (the tower's precision, bf16 or int8, picks the blocks' kernels in
-    eval_hip); bind_outputs lets the engine own the result tensors.  An evaluator
+    eval_hip, the batch picks their form: tile-parallel or persistent, the same bits); bind_outputs lets the engine own the result tensors.  An evaluator
     owns its tower — handle, packed weights, activation buffers, bound outputs — so every consumer of a net (a Player, a self-play
     engine, an arena) has one of its own; the net re-packs all of them when its weights change (DeepResNet._towers)."""
 
@@ -43,6 +43,14 @@ class _HipEvaluator(object):
 
     def __call__(self, x):
         return self.net.eval_hip(x, self.tower)
+
+    def eval(self, inputs):
+        """DeepResNet.eval's contract on this evaluator's tower (its precision, its scales): numpy float32 [B,3,S,S] -> numpy
+        (prob [B,S*S], value [B]), copied out.  B <= the evaluator's max_batch.  Player(pv_fn=ev.eval) recognises it like
+        DeepResNet.eval and plays on an evaluator of its own with this one's precision and scales."""
+        x = torch.from_numpy(np.ascontiguousarray(inputs, np.float32))
+        p, v = self(x.to(self.net.device))
+        return p.cpu().numpy().copy(), v.cpu().numpy().copy()     # (the tower's output tensors are overwritten by the next call)
 
     def bind_outputs(self, policy, value):
         if policy.shape[0] >= self.tower.max_batch:
@@ -232,8 +240,9 @@ class DeepResNet(object):
 
         precision="int8" (11x11 nets): the residual blocks run with int8 weights and int8 stored activations
         (csrc/af_tower_i8.hip, specified by alphafive_amd/tower_i8.py); stem, heads and dense layers stay bf16.  act_scales are
-        the 2 * blocks activation scales of calibrate_int8.  An int8 evaluator runs the persistent kernels at every batch — there
-        is no int8 small-batch form — so a position's bits do not depend on the batch it is evaluated in.  Weight updates
+        the 2 * blocks activation scales of calibrate_int8.  An int8 evaluator has the two forms a bf16 one has — the tile-parallel
+        kernel up to HipTower.small_batch_i8, the persistent kernels above — with the same bits (integer accumulation is exact in
+        any order), so a position's bits do not depend on the batch it is evaluated in.  Weight updates
         re-quantise the weights in place like the bf16 ones; the ACTIVATION scales stay as calibrated until the caller calibrates
         again (calibrate_int8 on the new weights, then evaluator.tower.enable_i8(scales))."""
         from . import tower_hip, tower_i8
@@ -249,15 +258,20 @@ class DeepResNet(object):
 
     @torch.no_grad()
     def eval_hip(self, x, tower=None):
-        """The whole forward on hand-written kernels: af_tower_stem -> af_tower_forward[_small] -> af_tower_heads (the 1x1 convs)
-        -> af_tower_dense (the three dense layers + softmax on the MFMA), on `tower` (default: the primary evaluator's).
+        """The whole forward on hand-written kernels: af_tower_stem -> af_tower_forward[_small] (an int8 tower:
+        af_tower_forward_i8[_small]) -> af_tower_heads (the 1x1 convs) -> af_tower_dense (the three dense layers + softmax on the
+        MFMA), on `tower` (default: the primary evaluator's).
         The one place that chooses the tower's form: the tile-parallel kernel up to the batch the library measured it faster at
-        (HipTower.small_batch), the persistent kernels above; the bits are the same either way."""
+        (HipTower.small_batch, for an int8 tower HipTower.small_batch_i8), the persistent kernels above; the bits are the same
+        either way."""
         tw = self._tower if tower is None else tower
         B = x.shape[0]
         tw.stem(x.contiguous())
         if tw.precision == "int8":
-            tw.forward_i8(B)                     # the persistent int8 kernels at every batch: no int8 small-batch form
+            if B <= tw.small_batch_i8:
+                tw.forward_i8_small(B)
+            else:
+                tw.forward_i8(B)
         elif B <= tw.small_batch:
             tw.forward_small(B)
         else:

@@ -119,7 +119,9 @@ class Player(object):
         # missing or its ABI does not match; nothing falls back to vendor ops.  pv_fn = DeepResNet.eval on a cuda device: the
         # same, through an evaluator of this Player's own (DeepResNet.evaluator(1): its own tower, so several Players and a
         # self-play engine can share one net) — one leaf per simulation is the batch the tile-parallel tower kernel is for.
-        # Any other owner with an eval_device() method is used as it is.
+        # pv_fn = the eval of an evaluator handed out by DeepResNet.evaluator / select_backend (network_deep._HipEvaluator) on a
+        # cuda net: the same again, on an evaluator of this Player's own with THAT evaluator's precision and activation scales —
+        # how an int8 tower plays.  Any other owner with an eval_device() method is used as it is.
         owner = getattr(pv_fn, "__self__", None)
         self._pv_owner = None
         self._pv_device = None
@@ -141,6 +143,12 @@ class Player(object):
                 self._pv_device, self._pv_owner, self.backend = fn, owner, "hip"
             else:
                 self._pv_device, self.backend = owner.eval_device, "device"
+        elif pv_fn is not None and owner is not None and getattr(pv_fn, "__name__", "") == "eval":
+            from .network_deep import _HipEvaluator
+            if isinstance(owner, _HipEvaluator) and owner.tower is not None and owner.net.device.type == "cuda":
+                fn = self._pv_close = owner.net.evaluator(1, precision=owner.tower.precision, act_scales=owner.tower.act_scales)
+                fn.bind_outputs(self._policy, self._value)
+                self._pv_device, self._pv_owner, self.backend = fn, owner.net, "hip"
         self.last_visits = None
 
     # -- player.py:37-46

@@ -58,6 +58,10 @@ def lib():
         L.af_tower_forward_i8.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
         L.af_tower_conv_i8.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32]
         L.af_tower_quantize_i8.argtypes = [vp, vp, vp, vp, C.c_int32]
+        L.af_tower_forward_i8_small.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
+        L.af_tower_conv_i8_small.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32]
+        L.af_tower_i8_small_batch.argtypes = [vp]
+        L.af_tower_i8_small_batch.restype = C.c_int32
         L.af_tower_i8_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
         L.af_tower_i8_debug_weights.restype = C.c_int64
         L.af_tower_strerror.argtypes = [C.c_int]
@@ -115,6 +119,7 @@ class HipTower(object):
         self._h = C.c_void_p()
         self.blocks = len(blocks)
         self.precision = precision
+        self.act_scales = None                         # int8: the scales last given to enable_i8, a float32 copy
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _check(lib().af_tower_create(board_size, width, len(blocks), idx, C.byref(self._h)), "af_tower_create")
         if precision == "int8":
@@ -139,6 +144,7 @@ class HipTower(object):
         self.pix = int(lib().af_tower_pix(self._h))
         self.flops_per_position = int(lib().af_tower_flops_per_position(self._h))
         self.small_batch = int(lib().af_tower_small_batch(self._h))       # forward_small is the faster form up to this batch (0: never)
+        self.small_batch_i8 = int(lib().af_tower_i8_small_batch(self._h))  # ... and forward_i8_small against forward_i8 (0: never, and at 15x15)
         # C8 activations [B][width/8][PIX][8]; zero borders are never written by the kernels
         self.x = torch.zeros((max_batch, width // 8, self.pix, 8), dtype=torch.bfloat16, device=self.device)
         self.g = torch.zeros_like(self.x)
@@ -226,12 +232,27 @@ class HipTower(object):
 
     def forward_i8(self, B):
         """The blocks in int8: quantises the stem's output in self.x, runs every block through xq / gq and leaves the last block's
-        bf16 output in self.x, where heads() reads it.  The persistent kernels at every batch."""
+        bf16 output in self.x, where heads() reads it.  The persistent kernels at every batch (forward_i8_small: the tile-parallel form)."""
         if self.precision != "int8":
             raise TowerError("forward_i8: this tower was built with precision=%r" % (self.precision,), -3)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _check(lib().af_tower_forward_i8(self._h, stream, self.x.data_ptr(), self.xq.data_ptr(), self.gq.data_ptr(), B),
                "af_tower_forward_i8")
+
+    def forward_i8_small(self, B):
+        """forward_i8() on the tile-parallel int8 kernel (af_tower_forward_i8_small): the same bits at any batch, the form
+        DeepResNet.eval_hip takes up to small_batch_i8."""
+        if self.precision != "int8":
+            raise TowerError("forward_i8_small: this tower was built with precision=%r" % (self.precision,), -3)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_forward_i8_small(self._h, stream, self.x.data_ptr(), self.xq.data_ptr(), self.gq.data_ptr(), B),
+               "af_tower_forward_i8_small")
+
+    def conv_i8_small(self, block, second, inp, inp2, out, B):
+        """Tests: one int8 layer on the tile-parallel kernel (af_tower_conv_i8_small); arguments as conv_i8."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_conv_i8_small(self._h, stream, block, int(second), inp.data_ptr(), inp2.data_ptr() if inp2 is not None else None,
+                                            out.data_ptr(), int(out.dtype == torch.bfloat16), B), "af_tower_conv_i8_small")
 
     def quantize_i8(self, x, xq, B):
         """Tests: the entry quantiser alone, bf16 C8 tensor x -> int8 C16 tensor xq."""

@@ -170,6 +170,18 @@ int af_tower_forward_i8(af_tower* t, void* stream, void* x_dev, void* xq_dev, vo
  * the last block's second convolution, which has no scale, is AF_TOWER_ERR_ARG.  Honours tune key 1. */
 int af_tower_conv_i8(af_tower* t, void* stream, int32_t block, int32_t second, const void* in_dev, const void* in2_dev, void* out_dev,
                      int32_t out_is_bf16, int32_t batch);
+/* af_tower_forward_i8 on the tile-parallel int8 kernel (af_tower_conv_i8_small): same arguments, same contract (asynchronous on
+ * `stream`, launches only, legal under stream capture, any batch >= 1, the same refusals), same bits — the int32 accumulator is
+ * exact in any order and the epilogue is the same sequence.  One workgroup per pixel tile of a position with the int8 weights
+ * streamed from the same fragment buffers, where af_tower_forward_i8 keeps them resident in persistent workgroups: the form for a
+ * handful of positions.  The entry quantiser is the same launch.  Tune key 1 does not reach it. */
+int af_tower_forward_i8_small(af_tower* t, void* stream, void* x_dev, void* xq_dev, void* gq_dev, int32_t batch);
+/* Tests: one layer on the tile-parallel kernel; arguments, contract and error codes of af_tower_conv_i8. */
+int af_tower_conv_i8_small(af_tower* t, void* stream, int32_t block, int32_t second, const void* in_dev, const void* in2_dev,
+                           void* out_dev, int32_t out_is_bf16, int32_t batch);
+/* The largest batch at which the library's measurement found af_tower_forward_i8_small faster than af_tower_forward_i8 (0: never,
+ * and on an S = 15 handle).  A constant; where it was measured: profiles/tower_int8_small.md. */
+int32_t af_tower_i8_small_batch(const af_tower* t);
 /* Tests: the entry quantiser alone, bf16 C8 -> int8 C16 at the scale of h_0. */
 int af_tower_quantize_i8(af_tower* t, void* stream, const void* x_dev, void* xq_dev, int32_t batch);
 /* Tests: af_tower_debug_weights for the int8 buffers, 4 * blocks + 1 of them: 4b + 0..3 = w1q, w2q (fragment streams, uint8

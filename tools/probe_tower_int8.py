@@ -2,12 +2,17 @@
 
     python tools/probe_tower_int8.py speed      # af_tower_forward_i8 against af_tower_forward, alternating in one process, + the quantiser alone
     python tools/probe_tower_int8.py quality    # bf16 hip path and int8 path against eval_device(dtype=float32) on 512 positions
+    python tools/probe_tower_int8.py small      # profiles/tower_int8_small.md: af_tower_forward_i8_small against af_tower_forward_i8 inside the
+                                                # whole evaluation (one graph per form, alternating replays), + the bf16 small form
+    python tools/probe_tower_int8.py player     # Player moves/s: int8 and bf16 through Player's own evaluator, numpy wrappers, eval_device
 
-Env: REPS (200 timed forwards per form and batch), BS ("8192,256"), BLOCKS (8), OUT (a file that gets the JSON as well)."""
+Env: REPS (200 timed forwards per form and batch), BS ("8192,256"), BLOCKS (8), OUT (a file that gets the JSON as well); small:
+REPLAYS (300), SMALL_BS ("1,2,4,8,16,32,64,128,256"); player: MOVES (16 timed moves per path and round), ROUNDS (2), SIMS ("500,642")."""
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -83,9 +88,124 @@ def quality():
     return out
 
 
+def _graph_of(tw, x, form):
+    """One whole evaluation — stem, (quantiser,) 2 * BLOCKS convolutions, heads, dense — as a captured graph."""
+    B = x.shape[0]
+
+    def run():
+        tw.stem(x)
+        getattr(tw, form)(B)
+        tw.heads(B)
+        tw.dense(B)
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        run()
+    return g
+
+
+def small():
+    """profiles/tower_small_batch.md's protocol for int8: per batch the forms alternate replay by replay in one process, each
+    replay between its own pair of events, after 20 warm-up replays."""
+    replays = int(os.environ.get("REPLAYS", 300))
+    bs = [int(b) for b in os.environ.get("SMALL_BS", "1,2,4,8,16,32,64,128,256").split(",")]
+    net = DeepResNet(S, blocks=BLOCKS, width=128, device="cuda", seed=1)
+    scales = net.calibrate_int8(_planes(256, 1))
+    bf, i8 = net.evaluator(max(bs)), net.evaluator(max(bs), precision="int8", act_scales=scales)
+    out = {"blocks": BLOCKS, "replays": replays, "small_batch_i8_in_library": i8.tower.small_batch_i8}
+    for B in bs:
+        x = _planes(B, B)
+        graphs = {"int8_persistent": (i8.tower, _graph_of(i8.tower, x, "forward_i8")), "int8_small": (i8.tower, _graph_of(i8.tower, x, "forward_i8_small")),
+                  "bf16_small": (bf.tower, _graph_of(bf.tower, x, "forward_small"))}
+        bits = {}
+        for name, (tw, g) in graphs.items():
+            for _ in range(20):
+                g.replay()
+            torch.cuda.synchronize()
+            bits[name] = (tw.policy[:B].clone(), tw.value[:B].clone())
+        same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(bits["int8_persistent"], bits["int8_small"]))
+        ev = {n: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(replays)] for n in graphs}
+        for r in range(replays):
+            for name, (_, g) in graphs.items():
+                e0, e1 = ev[name][r]
+                e0.record()
+                g.replay()
+                e1.record()
+        torch.cuda.synchronize()
+        row = {"int8_forms_same_bits": same}
+        for name in graphs:
+            row[name] = _stats(ev[name])
+        out["B%d" % B] = row
+        del graphs
+    net.close()
+    return out
+
+
+class _TorchOwner(object):
+    """An owner Player sends to eval_device (backend "device")."""
+
+    def __init__(self, net):
+        self.device, self.eval_device = net.device, net.eval_device
+
+    def eval(self, x):
+        p, v = self.eval_device(torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(self.device))
+        return p.float().cpu().numpy(), v.float().cpu().numpy()
+
+
+def player():
+    """profiles/tower_small_batch.md's Player protocol with the int8 paths added."""
+    sys.path.insert(0, os.path.join(R, "tests"))
+    from conftest import make_cfg
+    from alphafive_amd import utils
+    from alphafive_amd.player import Player
+    sims, cap = (int(v) for v in os.environ.get("SIMS", "500,642").split(","))
+    moves, rounds = int(os.environ.get("MOVES", 16)), int(os.environ.get("ROUNDS", 2))
+    net = DeepResNet(S, blocks=BLOCKS, width=128, device="cuda", seed=1)
+    scales = net.calibrate_int8(_planes(256, 1))
+    i8 = net.evaluator(1, precision="int8", act_scales=scales)
+    tw = i8.tower
+
+    def wrapper(form):
+        def f(x):
+            tw.stem(torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda())
+            getattr(tw, form)(1)
+            tw.heads(1)
+            p, v = tw.dense(1)
+            return p.cpu().numpy().copy(), v.cpu().numpy().copy()
+        return f
+    paths = {"int8_evaluator_eval_hip_graph": i8.eval, "deep_eval_bf16_hip_graph": net.eval,
+             "numpy_wrapper_int8_persistent_kernels": wrapper("forward_i8"), "numpy_wrapper_int8_small_kernels": wrapper("forward_i8_small"),
+             "eval_device_torch": _TorchOwner(net).eval}
+    cfg = make_cfg(board_size=S, simulation_per_step=sims, upper_simulation_per_step=cap)
+    out = {"sims": [sims, cap], "blocks": BLOCKS, "small_batch_i8_in_library": tw.small_batch_i8}
+    for rnd in range(rounds):
+        for name, fn in paths.items():
+            pl = Player(cfg, training=True, pv_fn=fn, seed=7, game_id=3)
+            state, last, over, n = pl.get_init_state(), None, False, 0
+            t0 = None
+            while not over and n < moves + 1:
+                if n == 1:                           # the first move (graph capture, lazy allocations) is warm-up
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                _, act = pl.get_action(state, last_action=last)
+                board = utils.step(utils.state_to_board(state, S), act)
+                state, last, n = utils.board_to_state(board), act, n + 1
+                over, _ = utils.is_game_over(board, cfg.goal)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            precision = getattr(getattr(pl._pv_device, "tower", None), "precision", None)
+            out.setdefault(name, {"backend": pl.backend, "own_tower_precision": precision, "rounds": []})["rounds"].append(
+                {"moves": n - 1, "seconds": round(dt, 3), "moves_per_s": round((n - 1) / dt, 2)})
+            pl.close()
+    net.close()
+    return out
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "speed"
-    res = {"speed": speed, "quality": quality}[what]()
+    res = {"speed": speed, "quality": quality, "small": small, "player": player}[what]()
     text = json.dumps(res, indent=1)
     print(text)
     if os.environ.get("OUT"):
