@@ -160,12 +160,14 @@ def test_closed_loop_self_play_replay_train_on_device(capsys, tmp_path):
     stack.close()
 
 
-@pytest.mark.parametrize("S, goal, sims, G, length", [(6, 4, 24, 48, 400), (11, 5, 12, 32, 900)])
+@pytest.mark.parametrize("S, goal, sims, G, length", [(6, 4, 24, 48, 400), (11, 5, 12, 32, 900), (13, 4, 8, 32, 900),
+                                                      (16, 4, 8, 32, 1200)])
 def test_device_to_device_hand_off_equals_the_host_path(S, goal, sims, G, length, capsys):
     """SURVEY 8f-1 / main.py:60-61: finished episodes go from the engine's pack kernels straight into the device replay ring
     (af_replay_append_packed: key -> board, policy, last move, value signs, construct_weights row) — the host reads only the
     header.  Same seeds => the same accept / duplicate / evict decisions and bit-identical batches as pushing the 5-tuples of
-    a twin engine into the host RandomStack."""
+    a twin engine into the host RandomStack.  S = 13 and 16: boards above 128 cells, whose keys carry four words per colour
+    (the engine's own pack kernels feeding the KW = 4 decode; crafted buffers: tests/test_gpu_replay_exact.py)."""
     import torch
     import pseudonet
     from conftest import make_cfg

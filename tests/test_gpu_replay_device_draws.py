@@ -121,9 +121,11 @@ def test_wrapped_ring():
     st.close()
 
 
-@pytest.mark.parametrize("S", [5, 11, 15])
+@pytest.mark.parametrize("S", [5, 11, 15, 3, 16])
 def test_gather_is_af_replay_samples(S):
-    """The returned (idx, turns, flip) fed to af_replay_sample give the very tensors draw_batches returned."""
+    """The returned (idx, turns, flip) fed to af_replay_sample give the very tensors draw_batches returned: the kernel against
+    itself behind its two front ends, on the smallest board and on C = 256 = the workgroup size too (what af_replay_sample's
+    tensors must be is tests/test_gpu_replay_exact.py's business)."""
     st, _ = _stack(S, 300, seed=S, draw_seed=S)
     for batches, num in ((1, 64), (4, 37)):
         got = st.draw_batches(num, batches, return_draws=True)

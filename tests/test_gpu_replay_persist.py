@@ -332,13 +332,12 @@ def test_reference_pickles_through_the_device_stack(tmp_path, monkeypatch, golde
 # ---------------------------------------------------------------------------------------------------------------------------
 # 7. what af_replay_append_packed stored, looked at directly
 # ---------------------------------------------------------------------------------------------------------------------------
-def test_device_to_device_hand_off_read_out_equals_the_host_records(capsys):
+def _hand_off_read_out(S, sims, G, length):
     import pseudonet
     from conftest import make_cfg
     from alphafive_amd.engine import SelfPlayEngine
     from alphafive_amd.replay import DeviceRandomStack
-    S, G, length = 6, 48, 400
-    cfg = make_cfg(board_size=S, goal=4, simulation_per_step=24, upper_simulation_per_step=32)
+    cfg = make_cfg(board_size=S, goal=4, simulation_per_step=sims, upper_simulation_per_step=sims + 8)
     mk = lambda: SelfPlayEngine(cfg, G, lambda x: pseudonet.pseudonet_torch(x, 321, 4096), device=0, seed=13)
     a, b = mk(), mk()
     host, dev = utils.RandomStack(S, length), DeviceRandomStack(S, length, device=0)
@@ -354,12 +353,24 @@ def test_device_to_device_hand_off_read_out_equals_the_host_records(capsys):
             else:
                 st.push_packed(sp.post_episodes_device(64), 64, cfg.gamma)
     dev.check()
-    capsys.readouterr()
     assert len(host.data) >= 200 and len(host.data_len) > 10
     _assert_same_stack(host, dev.to_host())
     a.close()
     b.close()
     dev.close()
+
+
+def test_device_to_device_hand_off_read_out_equals_the_host_records(capsys):
+    _hand_off_read_out(S=6, sims=24, G=48, length=400)
+    capsys.readouterr()
+
+
+@pytest.mark.parametrize("S, sims, G, length", [(13, 8, 32, 900), (16, 8, 32, 1200)])
+def test_device_to_device_hand_off_read_out_equals_the_host_records_on_four_word_boards(S, sims, G, length, capsys):
+    """The same on boards above 128 cells, whose keys carry four 64-bit words per colour: the engine's pack kernels feeding
+    af_replay_append_packed's KW = 4 decode, every stored record looked at."""
+    _hand_off_read_out(S, sims, G, length)
+    capsys.readouterr()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
