@@ -1386,6 +1386,18 @@ static TowerArgs layer_args(const af_tower* t, int b, bool second, void* x, void
     return a;
 }
 
+// One layer on the persistent kernels: what af_tower_forward is a loop over, and the hook of af_tower_i8.hip's device calibration.
+int af_tower_launch_layer(af_tower* t, hipStream_t st, int b, bool second, void* x_dev, void* g_dev, int batch) {
+    if (!t->set[b]) return AF_TOWER_ERR_STATE;
+    const int ncu = g_grid > 0 ? g_grid : t->ncu;
+    const int64_t units = (int64_t)batch * t->d.halves;      // what the persistent loop walks: positions, or their halves at 15x15
+    const int grid = units < ncu ? (int)units : ncu;
+    const ConvKernel* k = pick(t->S, g_engine, second, g_depth);
+    if (!k) return AF_TOWER_ERR_ARG;
+    hipLaunchKernelGGL(k->fn, dim3(grid), dim3(256), k->lds, st, layer_args(t, b, second, x_dev, g_dev, batch));
+    return AF_TOWER_OK;
+}
+
 extern "C" {
 
 int af_tower_tune(int32_t key, int32_t value) {
@@ -1555,15 +1567,10 @@ int64_t af_tower_plane_elems(const af_tower* t) { return t ? (int64_t)128 * t->d
 int af_tower_forward(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch) {
     if (!t || !x_dev || !g_dev || batch < 1) return AF_TOWER_ERR_ARG;
     for (int b = 0; b < t->blocks; ++b) if (!t->set[b]) return AF_TOWER_ERR_STATE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int ncu = g_grid > 0 ? g_grid : t->ncu;
-    const int64_t units = (int64_t)batch * t->d.halves;      // what the persistent loop walks: positions, or their halves at 15x15
-    const int grid = units < ncu ? (int)units : ncu;
     for (int b = 0; b < t->blocks; ++b)
         for (int second = 0; second < 2; ++second) {
-            const ConvKernel* k = pick(t->S, g_engine, second != 0, g_depth);
-            if (!k) return AF_TOWER_ERR_ARG;
-            hipLaunchKernelGGL(k->fn, dim3(grid), dim3(256), k->lds, st, layer_args(t, b, second != 0, x_dev, g_dev, batch));
+            const int rc = af_tower_launch_layer(t, static_cast<hipStream_t>(stream), b, second != 0, x_dev, g_dev, batch);
+            if (rc) return rc;
         }
     TW_HIP_OK(hipGetLastError());
     return AF_TOWER_OK;

@@ -101,6 +101,7 @@ struct af_tower {
     float* act = nullptr;           // [2][2 * blocks]: the activation scales a, then their reciprocals r
     float* keep = nullptr;          // every block's six fp32 source tensors as last packed: what a change of scales re-packs from
     mutable std::vector<char> qset; // per block: the int8 packers have run over it since the first enable (and the keep holds its sources)
+    uint32_t* cal = nullptr;        // device calibration: 2 * blocks absmax words (bf16 magnitude bits), then status and count (int32)
     template <class T> T* block(int b, int k) const { return reinterpret_cast<T*>(buf[4 * b + k]); }
     template <class T> T* end(int k) const { return reinterpret_cast<T*>(buf[4 * blocks + k]); }
 };
@@ -113,6 +114,11 @@ int af_tower_i8_carve(af_tower* t, char* p);
 // the int8 packers over blocks b0 .. b0 + nb - 1 from src (six device tensors per block, af_tower_update_device's order): called
 // behind the bf16 packers on the same stream wherever those run, when the handle is enabled.  Launches only.
 void af_tower_i8_pack(const af_tower* t, hipStream_t st, int b0, int nb, const float* const* src);
+
+// ---- af_tower_bf16.hip's part in the device calibration, called by af_tower_i8.hip ----
+// one bf16 layer of block b as af_tower_forward launches it (the persistent kernels under the tune keys, the same bits as every
+// other form): second = 0 is x -> g, second = 1 is (g, x) -> x.  Launches only.  AF_TOWER_ERR_STATE while block b has no weights.
+int af_tower_launch_layer(af_tower* t, hipStream_t st, int b, bool second, void* x_dev, void* g_dev, int batch);
 
 // tune key 1 of af_tower_tune (persistent workgroups; 0 = one per CU), which the int8 convolutions honour too
 int af_tower_grid_override();

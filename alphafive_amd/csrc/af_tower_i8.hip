@@ -30,7 +30,8 @@
 // af_tower_conv_i8_small<PROJ, OBF> is the same layer for a handful of positions, one workgroup per pixel tile with the weights
 // streamed (af_tower_forward_i8_small; its own comment, behind the kernel above; the same bits).
 //
-// The packers (af_tower_pack_i8_kernel) and the entry quantiser (af_tower_quantize_i8_kernel) are at the end, with the host part.
+// The packers (af_tower_pack_i8_kernel), the entry quantiser (af_tower_quantize_i8_kernel) and the kernels of the device
+// calibration (af_tower_absmax_kernel, af_tower_i8_finalize_kernel) are at the end, with the host part.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -479,6 +480,89 @@ __global__ __launch_bounds__(256) void af_tower_pack_i8_kernel(PackI8Args A) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Device calibration (af_tower_i8_calibrate; specified by tower_i8.scales_from_absmax / calibration_ok).
+//
+// Absmax of a bf16 C8 buffer over the BOARD pixels — units S .. S + NPIX - 1 of every channel octet, so the result does not rest
+// on the zero rows being zero — as the largest magnitude bit pattern: bits & 0x7fff orders bf16 values by magnitude as unsigned
+// integers, with the infinities (0x7f80) above every finite value and every NaN above them, so a NaN anywhere is seen.  A thread
+// takes one 16-byte unit per pass, kAbsUnroll passes of the grid in flight; the maximum is reduced per lane, per wave
+// (__shfl_xor), per workgroup (4 words of LDS) and leaves as ONE atomicMax per workgroup into the caller's word.  A maximum
+// does not depend on the order it is taken in: deterministic.  Every address is inside the first `batch` positions by
+// construction (i < batch * 16 * NPIX).
+constexpr int kAbsUnroll = 4;
+constexpr int kAbsMaxBlocks = 1024;
+__global__ __launch_bounds__(256) void af_tower_absmax_kernel(const char* x, uint32_t* word, int batch) {
+    __shared__ uint32_t red[4];
+    const int64_t total = (int64_t)batch * 16 * G::NPIX, stride = (int64_t)gridDim.x * 256;
+    uint32_t m = 0u;
+    for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += kAbsUnroll * stride) {
+        uint4 v[kAbsUnroll];
+#pragma unroll
+        for (int u = 0; u < kAbsUnroll; ++u) {
+            const int64_t i = i0 + u * stride;
+            v[u] = uint4{0u, 0u, 0u, 0u};
+            if (i < total) {
+                const int pos = (int)(i / (16 * G::NPIX)), rem = (int)(i - (int64_t)pos * (16 * G::NPIX));
+                const int k = rem / G::NPIX, n = rem - k * G::NPIX;     // k < 16, n < 121
+                v[u] = *reinterpret_cast<const uint4*>(x + (size_t)pos * kPlane8 + (uint32_t)(k * G::PIX + G::S + n) * 16u);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kAbsUnroll; ++u) {
+            const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t lo = w[e] & 0x7fffu, hi = (w[e] >> 16) & 0x7fffu;
+                m = m > lo ? m : lo;
+                m = m > hi ? m : hi;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, d, 64);
+        m = m > o ? m : o;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+        atomicMax(word, a > b ? a : b);
+    }
+}
+
+// the head of a calibration: its n absmax words start from 0
+__global__ __launch_bounds__(64) void af_tower_i8_clear_kernel(uint32_t* words, int n) {
+    for (int i = threadIdx.x; i < n; i += 64) words[i] = 0u;
+}
+
+// Its tail: one wave turns the n = 2 * blocks words into scales, in tower_i8.scales_from_absmax's operations — a = (absmax *
+// margin) / 127, 1 for an absmax of exactly 0, r = 1 / a — and installs them ALL OR NOT AT ALL: only if every absmax is finite and
+// every a finite and positive (calibration_ok) are act[0 .. n) = a and act[n .. 2n) = r written, status[0] = 0 and the counter
+// status[1] bumped; otherwise act stays as it was and status[0] = 1.  The vote is one __all over the wave, in front of any store.
+__global__ __launch_bounds__(64) void af_tower_i8_finalize_kernel(const uint32_t* words, float* act, int32_t* status, int n, float margin) {
+    bool ok = true;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const uint32_t bits = words[i];
+        const float amax = __uint_as_float(bits << 16);
+        const float a = bits == 0u ? 1.0f : __fdiv_rn(__fmul_rn(amax, margin), 127.0f);
+        ok = ok && bits < 0x7f80u && a > 0.0f && a < __builtin_inff();
+    }
+    const bool all_ok = __all(ok) != 0;
+    if (all_ok)
+        for (int i = threadIdx.x; i < n; i += 64) {
+            const uint32_t bits = words[i];
+            const float a = bits == 0u ? 1.0f : __fdiv_rn(__fmul_rn(__uint_as_float(bits << 16), margin), 127.0f);
+            act[i] = a;
+            act[n + i] = __fdiv_rn(1.0f, a);
+        }
+    if (threadIdx.x == 0) {
+        status[0] = all_ok ? 0 : 1;
+        if (all_ok) status[1] = status[1] + 1;
+    }
+}
+
 // ------------------------------------------------------------------ host ------------------------------------------------------------------
 enum { kW1q, kW2q, kMb1, kMb2 };
 constexpr int64_t kQBytes[4] = {2 * 72 * 64 * 16, 2 * 80 * 64 * 16, 2 * 128 * 4, 2 * 128 * 4};
@@ -506,6 +590,7 @@ constexpr int32_t kSmallBatchI8 = 64;
 
 size_t padded(int64_t bytes) { return (size_t)((bytes + 255) & ~(int64_t)255); }
 int64_t act_bytes(const af_tower* t) { return (int64_t)4 * t->blocks * 4; }
+int64_t cal_bytes(const af_tower* t) { return (int64_t)(2 * t->blocks + 2) * 4; }       // the absmax words, status, count
 
 bool ready(const af_tower* t) {
     if (!t->i8) return false;
@@ -546,11 +631,18 @@ void launch_quantize(af_tower* t, hipStream_t st, const void* x, void* xq, int b
                        static_cast<const char*>(x), static_cast<char*>(xq), t->act + 2 * t->blocks, batch);
 }
 
+// the grid from the batch, capped as launch_quantize's: a thread takes kAbsUnroll units per pass
+void launch_absmax(hipStream_t st, const void* x, uint32_t* word, int batch) {
+    const int64_t blocks = ((int64_t)batch * 16 * G::NPIX + 256 * kAbsUnroll - 1) / (256 * kAbsUnroll);
+    hipLaunchKernelGGL(af_tower_absmax_kernel, dim3((unsigned)(blocks < kAbsMaxBlocks ? blocks : kAbsMaxBlocks)), dim3(256), 0, st,
+                       static_cast<const char*>(x), word, batch);
+}
+
 }  // namespace
 
 size_t af_tower_i8_arena_bytes(const af_tower* t) {
     if (t->S != 11) return 0;
-    size_t total = padded(act_bytes(t)) + padded(kKeepFloats * 4) * (size_t)t->blocks;
+    size_t total = padded(act_bytes(t)) + padded(cal_bytes(t)) + padded(kKeepFloats * 4) * (size_t)t->blocks;
     for (int k = 0; k < 4; ++k) total += padded(kQBytes[k]) * (size_t)t->blocks;
     return total;
 }
@@ -564,6 +656,8 @@ int af_tower_i8_carve(af_tower* t, char* p) {
     for (int b = 0; b < t->blocks; ++b)
         for (int k = 0; k < 4; ++k) { t->qbuf.push_back(p); p += padded(kQBytes[k]); }
     t->act = reinterpret_cast<float*>(p); p += padded(act_bytes(t));
+    t->cal = reinterpret_cast<uint32_t*>(p); p += padded(cal_bytes(t));
+    TW_HIP_OK(hipMemset(t->cal, 0, (size_t)cal_bytes(t)));              // status 0, no calibration counted yet
     t->keep = reinterpret_cast<float*>(p);
     t->qset.assign(t->blocks, 0);
     return AF_TOWER_OK;
@@ -674,6 +768,51 @@ int af_tower_forward_i8_small(af_tower* t, void* stream, void* x_dev, void* xq_d
 }
 
 int32_t af_tower_i8_small_batch(const af_tower* t) { return t && t->S == 11 ? kSmallBatchI8 : 0; }
+
+// ---- activation scales without the host ----
+int af_tower_i8_calibrate(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch, float margin) {
+    if (!t || t->S != 11 || !x_dev || !g_dev || batch < 1 || !(margin > 0.0f) || !std::isfinite(margin)) return AF_TOWER_ERR_ARG;
+    if (!ready(t)) return AF_TOWER_ERR_STATE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int n = 2 * t->blocks;
+    hipLaunchKernelGGL(af_tower_i8_clear_kernel, dim3(1), dim3(64), 0, st, t->cal, n);
+    // the bf16 tower's own forward, every stored activation measured on its way: h_b in front of block b, g_b between its layers
+    for (int b = 0; b < t->blocks; ++b) {
+        launch_absmax(st, x_dev, t->cal + 2 * b, batch);
+        int rc = af_tower_launch_layer(t, st, b, false, x_dev, g_dev, batch);
+        if (rc) return rc;
+        launch_absmax(st, g_dev, t->cal + 2 * b + 1, batch);
+        rc = af_tower_launch_layer(t, st, b, true, x_dev, g_dev, batch);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(af_tower_i8_finalize_kernel, dim3(1), dim3(64), 0, st, t->cal, t->act, reinterpret_cast<int32_t*>(t->cal + n), n, margin);
+    // ... and every block again from the sources the handle kept, under the scales now in place (a refused calibration: the
+    // same bytes once more)
+    std::vector<const float*> src(6 * (size_t)t->blocks);
+    for (int b = 0; b < t->blocks; ++b)
+        for (int i = 0; i < 6; ++i) src[6 * b + i] = keep_of(t, b) + keep_off(i);
+    af_tower_i8_pack(t, st, 0, t->blocks, src.data());
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
+
+int af_tower_i8_calibration_status(af_tower* t, int32_t* status, int32_t* count) {
+    if (!t || t->S != 11 || !status || !count) return AF_TOWER_ERR_ARG;
+    if (!t->i8) return AF_TOWER_ERR_STATE;
+    int32_t h[2];
+    TW_HIP_OK(hipSetDevice(t->device));
+    TW_HIP_OK(hipDeviceSynchronize());
+    TW_HIP_OK(hipMemcpy(h, t->cal + 2 * t->blocks, sizeof(h), hipMemcpyDeviceToHost));
+    *status = h[0]; *count = h[1];
+    return AF_TOWER_OK;
+}
+
+int af_tower_i8_absmax(af_tower* t, void* stream, const void* x_dev, int32_t batch, uint32_t* word_dev) {
+    if (!t || t->S != 11 || !x_dev || !word_dev || batch < 1) return AF_TOWER_ERR_ARG;
+    launch_absmax(static_cast<hipStream_t>(stream), x_dev, word_dev, batch);
+    TW_HIP_OK(hipGetLastError());
+    return AF_TOWER_OK;
+}
 
 int64_t af_tower_i8_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes) {
     if (!t || t->S != 11 || index < 0 || index > 4 * t->blocks) return AF_TOWER_ERR_ARG;

@@ -164,18 +164,26 @@ class DeepResNet(object):
         self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     @torch.no_grad()
-    def set_variables_device(self, tensors):
+    def set_variables_device(self, tensors, calibrate_on=None, margin=1.0):
         """set_variables without the host: `tensors` maps every name to a float32 tensor (a deep Trainer's parameters:
         train.Trainer.device_variables()).  With a hip backend selected the net's own tensors take the values in self.dtype in place
         (one copy_ per variable, so eval_device follows), and HipTower.load_device packs in place, stream-ordered, with no wait:
         the kernels straight from the caller's tensors — the packed buffers are the snapshot, no weight tensor is cloned — and the
         biases from small fp32 temporaries made of the net's rounded copies.  The tower adds the stem's, blocks' and head
         convolutions' biases in fp32 as given, so handing over the rounded values is what makes host path and device path pack
-        the same values and give the same bits.  A cpu net, or one without a hip backend, does what set_variables does."""
+        the same values and give the same bits.  A cpu net, or one without a hip backend, does what set_variables does.
+
+        calibrate_on: planes (float32 [B,3,11,11] on the device) to re-calibrate the int8 evaluators' activation scales on, behind
+        load_device on the same stream (calibrate_int8_device without a second version bump): the whole hand-over stays launches
+        only, and an int8 evaluator follows the new net with scales measured on it.  None (default): the scales stay as they are —
+        today's behaviour and bits.  The host path ignores it (there is no tower to calibrate)."""
         towers = self._towers()
         if self.device.type != "cuda" or not towers:
             self.set_variables(tensors)
             return
+        if calibrate_on is not None:
+            from . import tower_hip
+            tower_hip.check_calibration("int8", self.board_size, margin)     # refused before anything is written
         src = collections.OrderedDict()
         for name in self._checked(tensors):
             src[name] = tensors[name].detach().to(device=self.device, dtype=torch.float32).contiguous()   # no copy if it already is
@@ -186,6 +194,10 @@ class DeepResNet(object):
                 src[name] = own.float()
         for tower in towers:
             tower.load_device(src)
+        if calibrate_on is not None:
+            for tower in towers:
+                if tower.precision == "int8":
+                    tower.calibrate_i8(calibrate_on, margin)
         self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     def save_npz(self, path):
@@ -244,7 +256,9 @@ class DeepResNet(object):
         kernel up to HipTower.small_batch_i8, the persistent kernels above — with the same bits (integer accumulation is exact in
         any order), so a position's bits do not depend on the batch it is evaluated in.  Weight updates
         re-quantise the weights in place like the bf16 ones; the ACTIVATION scales stay as calibrated until the caller calibrates
-        again (calibrate_int8 on the new weights, then evaluator.tower.enable_i8(scales))."""
+        again, which needs the host no more than the weights do: calibrate_int8_device(planes), or
+        set_variables_device(tensors, calibrate_on=planes) in one go, measures the new net's activations on the device and installs
+        the scales in place, launches only (the host route — calibrate_int8, then evaluator.tower.enable_i8(scales) — remains)."""
         from . import tower_hip, tower_i8
         tower_hip.check_precision(precision, self.board_size, act_scales)
         if precision == "int8":
@@ -297,6 +311,28 @@ class DeepResNet(object):
         scales = (amax * float(margin) / 127.0).astype(np.float32)
         scales[scales == 0] = 1.0
         return scales
+
+    @torch.no_grad()
+    def calibrate_int8_device(self, planes, margin=1.0, evaluators=None):
+        """calibrate_int8 + enable_i8 without the host (HipTower.calibrate_i8): planes float32 [B,3,11,11] on the net's device;
+        every int8 evaluator of the net — or those given — measures the activations of its own bf16 kernels over them, on its own
+        handle (towers are independent), turns the maxima into scales on the device and re-packs its int8 weights under them, on
+        torch's current stream with no wait.  What is measured is the bf16 tower, not calibrate_int8's fp32 path
+        (alphafive_amd/tower_i8.py).  Whether a tower installed its scales: evaluator.tower.calibration_status().  ValueError,
+        before anything touches the GPU, for a bad margin, a 15x15 net, a bf16 evaluator among those given, or no int8 evaluator."""
+        from . import tower_hip
+        tower_hip.check_calibration("int8", self.board_size, margin)
+        if evaluators is None:
+            towers = [tw for tw in self._towers() if tw.precision == "int8"]
+        else:
+            towers = [ev.tower for ev in evaluators]
+        if not towers:
+            raise ValueError("calibrate_int8_device: the net has no int8 evaluator")
+        for tw in towers:
+            tower_hip.check_calibration(tw.precision, tw.S, margin)
+        for tw in towers:
+            tw.calibrate_i8(planes, margin)
+        self._pack_version = getattr(self, "_pack_version", 0) + 1
 
     def eval(self, inputs):
         """network.py:90-97, as ResNet.eval: numpy float32[B,3,S,S] -> (prob[B,S*S], value[B]) numpy.  A cuda net evaluates on the

@@ -64,6 +64,9 @@ def lib():
         L.af_tower_i8_small_batch.restype = C.c_int32
         L.af_tower_i8_debug_weights.argtypes = [vp, C.c_int32, vp, C.c_int64]
         L.af_tower_i8_debug_weights.restype = C.c_int64
+        L.af_tower_i8_calibrate.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_float]
+        L.af_tower_i8_calibration_status.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.af_tower_i8_absmax.argtypes = [vp, vp, vp, C.c_int32, vp]
         L.af_tower_strerror.argtypes = [C.c_int]
         L.af_tower_strerror.restype = C.c_char_p
         _lib = L
@@ -102,6 +105,18 @@ def check_precision(precision, board_size, act_scales):
         raise ValueError("act_scales given with precision=%r" % (precision,))
 
 
+def check_calibration(precision, board_size, margin):
+    """What a device calibration (HipTower.calibrate_i8) can be asked for, checked before anything touches the GPU: ValueError
+    for a tower that is not int8, for a board other than 11x11 and for a margin that is not a finite positive number."""
+    if precision != "int8":
+        raise ValueError("device calibration needs a precision='int8' tower, not %r" % (precision,))
+    if board_size != 11:
+        raise ValueError("precision='int8' is built for 11x11 boards only, not %dx%d" % (board_size, board_size))
+    m = float(margin)
+    if not (np.isfinite(m) and m > 0):
+        raise ValueError("device calibration: margin must be finite and positive, not %r" % (margin,))
+
+
 def tune(key, value):
     _check(lib().af_tower_tune(key, value), "af_tower_tune")
 
@@ -119,7 +134,9 @@ class HipTower(object):
         self._h = C.c_void_p()
         self.blocks = len(blocks)
         self.precision = precision
-        self.act_scales = None                         # int8: the scales last given to enable_i8, a float32 copy
+        # int8: the scales last given to enable_i8, a float32 copy — the last HOST-given ones: a device calibration
+        # (calibrate_i8) replaces the scales on the device without telling the host; read_act_scales() reads those back
+        self.act_scales = None
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _check(lib().af_tower_create(board_size, width, len(blocks), idx, C.byref(self._h)), "af_tower_create")
         if precision == "int8":
@@ -229,6 +246,52 @@ class HipTower(object):
         a = np.ascontiguousarray(np.asarray(act_scales, np.float32).reshape(-1))
         _check(lib().af_tower_i8_enable(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0]), "af_tower_i8_enable")
         self.act_scales = a.copy()
+
+    def calibrate_i8(self, planes, margin=1.0):
+        """Activation scales from the device's own activations, in place (af_tower_i8_calibrate): runs the stem over planes —
+        float32 [B,3,11,11], contiguous, on this device — then the bf16 blocks with the absmax of every h_b and g_b measured on the
+        way, turns the 2 * blocks maxima into scales on the device (tower_i8.scales_from_absmax), installs them if they are all
+        usable (calibration_status() tells) and re-packs the int8 weights under them.  Launches only on torch's current stream: no
+        allocation, no copy to the host, no wait, so with B <= max_batch — the tower's own x / g — it is legal inside a stream
+        capture, and an int8 forward captured earlier replays with the new scales.  A larger B runs through scratch buffers
+        allocated for the call: NOT for use under capture.  x (and the scratch g) are left holding the bf16 tower's activations."""
+        check_calibration(self.precision, self.S, margin)
+        if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.float32 and planes.is_contiguous()
+                and planes.dim() == 4 and tuple(planes.shape[1:]) == (3, self.S, self.S) and planes.shape[0] >= 1):
+            raise TowerError("calibrate_i8: planes must be a contiguous float32 [B,3,%d,%d] tensor on %s" % (self.S, self.S, self.device))
+        B = planes.shape[0]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if B <= self.max_batch:
+            x, g = self.x, self.g
+        else:
+            x = torch.zeros((B,) + tuple(self.x.shape[1:]), dtype=torch.bfloat16, device=self.device)
+            g = torch.zeros_like(x)
+        _check(lib().af_tower_stem(self._h, stream, planes.data_ptr(), x.data_ptr(), B), "af_tower_stem")
+        _check(lib().af_tower_i8_calibrate(self._h, stream, x.data_ptr(), g.data_ptr(), B, float(margin)), "af_tower_i8_calibrate")
+
+    def calibration_status(self):
+        """-> (status, count) of af_tower_i8_calibration_status: 0 if the last calibrate_i8 installed its scales, 1 if it refused
+        them (a NaN or an infinity among the activations) and left the old ones; how many have been installed.  Synchronises."""
+        st, n = C.c_int32(), C.c_int32()
+        _check(lib().af_tower_i8_calibration_status(self._h, C.byref(st), C.byref(n)), "af_tower_i8_calibration_status")
+        return st.value, n.value
+
+    def read_act_scales(self):
+        """The activation scales as the device holds them now, float32 [2 * blocks] in tower_i8's order — after a calibrate_i8
+        these are not act_scales any more.  Synchronises the device."""
+        size = lib().af_tower_i8_debug_weights(self._h, 4 * self.blocks, None, 0)
+        _check(size, "af_tower_i8_debug_weights")
+        buf = np.empty(size, np.uint8)
+        _check(lib().af_tower_i8_debug_weights(self._h, 4 * self.blocks, buf.ctypes.data_as(C.c_void_p), size), "af_tower_i8_debug_weights")
+        return buf.view(np.float32)[:2 * self.blocks].copy()
+
+    def absmax(self, x, B):
+        """Tests: the absmax kernel alone over the board pixels of the first B positions of a bf16 C8 tensor -> the largest
+        magnitude's bit pattern (bits & 0x7fff), an int.  Synchronises."""
+        word = torch.zeros(1, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check(lib().af_tower_i8_absmax(self._h, stream, x.data_ptr(), B, word.data_ptr()), "af_tower_i8_absmax")
+        return int(word.item())
 
     def forward_i8(self, B):
         """The blocks in int8: quantises the stem's output in self.x, runs every block through xq / gq and leaves the last block's

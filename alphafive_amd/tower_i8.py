@@ -7,6 +7,14 @@ ACTIVATION SCALES.  One fp32 scale `a` per stored int8 tensor, 2 * blocks of the
 g_{blocks-1}: h_b is the input of block b, g_b the output of its first convolution.  The last block's output stays bf16 and has
 none.  The kernels multiply by r = fp32(1 / a) (one fp32 division).
 
+SCALES FROM ACTIVATIONS (scales_from_absmax, calibration_ok).  A scale comes from the absmax of the tensor it belongs to, over all
+board pixels of all positions of a calibration batch:  a = fp32(fp32(absmax * margin) / 127), a = 1 for an absmax of exactly 0,
+r = fp32(1 / a).  A set of 2 * blocks scales is usable iff every absmax is finite and every a finite and positive.  The DEVICE
+calibration (af_tower_i8_calibrate, HipTower.calibrate_i8) measures the bf16 kernels' own stored activations — the h_b and g_b
+the bf16 tower (csrc/af_tower_bf16.hip) writes for the same planes, exact bf16 values, so their absmax is exact — and applies
+these operations in a kernel, held to them bit for bit.  DeepResNet.calibrate_int8 measures the fp32 PyTorch path instead and
+does its arithmetic in fp64 on the host: the two agree to about the bf16 path's own distance from fp32, not to the bit.
+
 ENTRY.  The stem's bf16 output x becomes int8 by  q = clamp(rint(fp32(x) * r_h0), -127, 127), rint = round half to even.
 
 WEIGHTS of a block's first convolution, per cout c over its 1152 weights w (fp32):
@@ -70,6 +78,26 @@ def check_scales(act_scales, blocks):
 def reciprocal(a):
     """r = fp32(1 / a)."""
     return f32(1.0) / np.asarray(a, np.float32)
+
+
+def scales_from_absmax(absmax, margin):
+    """absmax [n] (any float dtype; bf16 values on the device route) -> (a, r), float32 [n] each: a = fdiv(fmul(absmax, margin), 127),
+    1 where absmax is exactly 0; r = fdiv(1, a).  Every step one fp32 operation.  Values that calibration_ok refuses (NaN,
+    infinities) pass through as IEEE arithmetic makes them."""
+    x = np.asarray(absmax, np.float32).reshape(-1)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        a = ((x * f32(margin)).astype(np.float32) / f32(QMAX)).astype(np.float32)
+        a = np.where(x == 0, f32(1.0), a).astype(np.float32)
+        r = (f32(1.0) / a).astype(np.float32)
+    return a, r
+
+
+def calibration_ok(absmax, margin):
+    """True iff every absmax is finite and every scale scales_from_absmax makes of it is finite and positive: the condition under
+    which the device calibration installs its scales (all of them, or none)."""
+    x = np.asarray(absmax, np.float32).reshape(-1)
+    a, _ = scales_from_absmax(x, margin)
+    return bool(np.isfinite(x).all() and np.isfinite(a).all() and (a > 0).all())
 
 
 def quantize_activation(x, r):

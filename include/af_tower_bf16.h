@@ -189,6 +189,32 @@ int af_tower_quantize_i8(af_tower* t, void* stream, const void* x_dev, void* xq_
  * reciprocals.  AF_TOWER_ERR_STATE before enable or for a block without int8 weights. */
 int64_t af_tower_i8_debug_weights(af_tower* t, int32_t index, void* host_out, int64_t cap_bytes);
 
+/* Activation scales without the host.  x_dev holds the stem's bf16 C8 output for `batch` positions, as for af_tower_forward; g_dev
+ * is scratch of the same size; the zero borders of both must be zero.  The call runs the BF16 tower's forward over them, layer by
+ * layer on the kernels of af_tower_forward, and takes the absmax of every stored activation on its way — h_b, the input of block b
+ * (h_0 = the stem's output), and g_b, the output of its first convolution, each over all board pixels of all positions, exact
+ * because the values are bf16 — into 2 * blocks words inside the handle's allocation.  One small kernel then turns them into
+ * scales as alphafive_amd/tower_i8.py states it (scales_from_absmax: a = (absmax * margin) / 127 in fp32, 1 for an absmax of 0,
+ * r = 1 / a) and installs them all or not at all: if every absmax is finite and every a finite and positive, the scales and
+ * reciprocals of af_tower_i8_enable's table are overwritten in place, the status is 0 and the calibration counter goes up by one;
+ * otherwise (a NaN or an infinity among the activations, a product that overflows) the table stays as it was and the status is
+ * 1.  Last, the int8 packers re-pack every block from the fp32 sources the handle kept, under the scales then in place.
+ * AF_TOWER_ERR_ARG for a null argument, an S = 15 handle, batch < 1 or a margin that is not finite and positive;
+ * AF_TOWER_ERR_STATE before af_tower_i8_enable or while a block has no int8 weights (af_tower_forward_i8's condition).
+ * The call is launches only, stream-ordered on `stream`: nothing is allocated, freed or copied to the host, nothing waits, and
+ * no scale-derived value is a kernel argument.  It is therefore legal under stream capture, and
+ *   - an int8 forward graph captured before it replays with the new scales and the re-packed weights;
+ *   - [af_tower_update_device; af_tower_stem; af_tower_i8_calibrate] may itself be captured and replayed over changed tensors.
+ * x_dev ends up holding the bf16 tower's output, g_dev the last block's mid activation. */
+int af_tower_i8_calibrate(af_tower* t, void* stream, void* x_dev, void* g_dev, int32_t batch, float margin);
+/* What the last af_tower_i8_calibrate on this handle found (0 installed, 1 refused; 0 before the first) and how many have been
+ * installed since af_tower_create.  Synchronises the device, like the debug reads.  AF_TOWER_ERR_STATE before enable. */
+int af_tower_i8_calibration_status(af_tower* t, int32_t* status, int32_t* count);
+/* Tests: the absmax kernel alone.  The largest bf16 magnitude among the board pixels of x_dev's first `batch` positions, as its
+ * bit pattern (bits & 0x7fff: 0x7f80 is an infinity, anything above a NaN), is max-ed into *word_dev, a device word the caller
+ * has cleared.  Needs no enable.  Asynchronous on `stream`. */
+int af_tower_i8_absmax(af_tower* t, void* stream, const void* x_dev, int32_t batch, uint32_t* word_dev);
+
 int64_t af_tower_flops_per_position(const af_tower* t);   /* 2*MAC of the tower, direct convolution */
 const char* af_tower_strerror(int code);
 
