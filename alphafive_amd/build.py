@@ -23,6 +23,8 @@ TARGETS = {
     "libaf_replay.so": (["csrc/af_replay.hip"], []),
     # the trainer's Adam is held to a numpy specification bit for bit (train_hip.adam_reference): as written, too
     "libaf_train.so": (["csrc/af_train.hip"], ["-ffp-contract=off"]),
+    # the symmetry average is seven additions and one multiplication in a stated order (symmetry.reduce_reference): as written
+    "libaf_sym.so": (["csrc/af_sym.hip"], ["-ffp-contract=off"]),
 }
 
 

@@ -431,6 +431,9 @@ class SelfPlayEngine:
         # the graph loop and is cleared, stream-ordered, in front of the first tick that sees a new version.
         self._memo_version = None
         if eval_memo:
+            if not getattr(pv_device, "deterministic", True):
+                raise EngineError("eval_memo: the evaluator is not a pure function of the planes (deterministic is False: "
+                                  "symmetry.SymmetricEvaluator(mode='random') draws per leaf); the memo would freeze one draw")
             if self._weights_version is None:
                 raise EngineError("eval_memo: the evaluator exposes no weights_version (the memo could not tell when to forget); "
                                   "pass SelfPlayEngine(..., weights_version=lambda: net.version)")

@@ -145,10 +145,17 @@ class Player(object):
                 self._pv_device, self.backend = owner.eval_device, "device"
         elif pv_fn is not None and owner is not None and getattr(pv_fn, "__name__", "") == "eval":
             from .network_deep import _HipEvaluator
+            from .symmetry import SymmetricEvaluator
             if isinstance(owner, _HipEvaluator) and owner.tower is not None and owner.net.device.type == "cuda":
                 fn = self._pv_close = owner.net.evaluator(1, precision=owner.tower.precision, act_scales=owner.tower.act_scales)
                 fn.bind_outputs(self._policy, self._value)
                 self._pv_device, self._pv_owner, self.backend = fn, owner.net, "hip"
+            elif isinstance(owner, SymmetricEvaluator) and owner.device.type == "cuda":
+                # pv_fn = the eval of a symmetry.SymmetricEvaluator: this Player's leaf under all eight symmetries (or one drawn
+                # per leaf) on a copy of its own — in mean mode the eight rows ride in the one small-batch launch a single leaf takes
+                fn = self._pv_close = owner.copy(1)
+                fn.bind_outputs(self._policy, self._value)
+                self._pv_device, self._pv_owner, self.backend = fn, fn, "hip"
         self.last_visits = None
 
     # -- player.py:37-46
